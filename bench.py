@@ -1,7 +1,12 @@
 """Benchmark: CSWin-UNet training throughput (images/sec) at 512x512 bf16, batch 16 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1 is launched by the driver with torch.distributed.run (one process per GPU, RCCL).
+A plain run sets up, warms up, times K steps and prints the result line (its "roofline",
+"cpu_baseline" and "reference_architecture" are then null / absent); --full adds the legs described
+below (roofline, cpu_baseline, the second timed run of the reference architecture).  --dump-outputs
+DIR writes what the last timed step returned (loss, output probabilities, Dice / IoU sums) as
+DIR/<name>.npy (float32); the weights, batches and step order depend only on the arguments.
 One step = forward + BCE (with the reference loop's per-step thresholded Dice / IoU sums, cswin:789-795,
 fused into the loss kernel) + backward (+ bucketed RCCL gradient all-reduce, captured in the same HIP
 graph, csu.dist.GradAllReduce) + fused AdamW on a batch of
@@ -61,12 +66,18 @@ def parse():
                     help="SimAM gate on the skip features: the CSWin-SimAM-UNet of BASELINE configs[2] (default); "
                          "--no-simam: the reference's own architecture (train_cswinunet_segmentation.py has no SimAM)")
     ap.add_argument("--no-ref-arch", action="store_true",
-                    help="skip the second timed run of the reference architecture (no SimAM) that a SimAM bench "
-                         "line carries as 'reference_architecture' (N = 1 only)")
+                    help="with --full: skip the second timed run of the reference architecture (no SimAM) that a "
+                         "SimAM bench line carries as 'reference_architecture' (N = 1 only)")
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="drop_rate = attn_drop_rate = drop_path_rate (the reference main() trains at 0.3, cswin:930-932)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "on", "off"])
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs a plain run leaves out: the per-kernel roofline ledger, the CPU baseline "
+                         "and the second timed run of the reference architecture (each still has its own off switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; a larger array as a fixed seeded sample)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "on", "off"], help="with --full")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="capture the whole step in a HIP graph (N > 1: with the bucketed all-reduce; off: eager DDP)")
     ap.add_argument("--bucket-mb", type=float, default=32.0, help="gradient all-reduce bucket size (N > 1)")
@@ -94,6 +105,25 @@ def synthetic_batches(n, batch, img, device, seed):
         x, t = ellipse_batch(rng, batch, img)
         out.append((x.to(device), t.to(device)))
     return out
+
+
+DUMP_LIMIT = 64 << 20   # bytes of all --dump-outputs files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy in float32.  The smallest
+    arrays go first and each may take an equal share of what is left of DUMP_LIMIT; one that does not
+    fit is written as a sample of its flattened values at fixed (seed 0) sorted positions."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in arrays.items()}
+    left = DUMP_LIMIT - 4096 * len(host)    # .npy headers
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def _cpu_model():
@@ -255,17 +285,19 @@ def main():
         opt = make_optimizer(model, capturable=use_graph)
     batches = synthetic_batches(2, args.batch, args.img, device, seed=1234 + rank)
     amp = torch.bfloat16 if dtype == torch.bfloat16 else None
+    last = {}
 
     def eager_step(i):
         x, t = batches[i % len(batches)]
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp is not None):
             y = model(x)
-        loss, _ = bce_loss_stats(y, t)   # + the reference loop's per-step Dice / IoU sums (cswin:789-795)
+        loss, stats = bce_loss_stats(y, t)   # + the reference loop's per-step Dice / IoU sums (cswin:789-795)
         loss.backward()
         if reducer is not None:
             reducer.finish()
         opt.step()
+        last["output"], last["stats"] = y.detach(), stats   # for --dump-outputs (no autograd graph kept)
         return loss
 
     if not use_graph and not args.side_wgrad:
@@ -294,8 +326,9 @@ def main():
     # replayed step; the per-launch bracket cost is calibrated against the plain replays.  Eager
     # bench: every launch of 2 eager steps, timed with HIP events on its launch stream.
     ledger = None
-    graph_ledger = use_graph and not args.no_roofline
-    if not args.no_roofline and not graph_ledger:
+    roofline = args.full and not args.no_roofline
+    graph_ledger = use_graph and roofline
+    if roofline and not graph_ledger:
         from csu.ledger import KernelLedger
         ledger = KernelLedger(repeat=4)
         side, ops.SIDE_WGRAD = ops.SIDE_WGRAD, False   # serialized, like the single-stream graph replay
@@ -323,6 +356,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
     images = args.batch * world * args.steps
+    if args.dump_outputs and rank == 0:
+        # before the --full legs: their captures train the same model on
+        if use_graph:
+            last = {"output": gstep.out, "stats": gstep.stats}
+        dump_outputs(args.dump_outputs, dict(last, loss=loss))
     lsteps = 2
     ledger_step_ms = None
     if graph_ledger and rank == 0:
@@ -362,10 +400,11 @@ def main():
             roof["ledger_step_ms"] = round(ledger_step_ms, 3)
         roof["ledger"] = "graph replays (external HIP event nodes)" if graph_ledger else "eager steps (HIP events)"
     ref_arch = None
-    if (args.model == "cswin" and args.simam and world == 1 and not dp and use_graph and not args.no_ref_arch):
+    if (args.full and args.model == "cswin" and args.simam and world == 1 and not dp and use_graph
+            and not args.no_ref_arch):
         ref_arch = _time_ref_arch(args, device, amp, batches, depth, split, pd)
     cpu = None
-    if rank == 0 and world == 1 and (args.cpu_baseline == "on" or (args.cpu_baseline == "auto")):
+    if args.full and rank == 0 and world == 1 and (args.cpu_baseline == "on" or (args.cpu_baseline == "auto")):
         try:
             cpu = (cpu_baseline_unet if args.model == "unet" else cpu_baseline)(args, dtype)
         except Exception as e:  # baseline is informational; never hide the GPU number
@@ -451,6 +490,9 @@ def _bench_train_model(args, model, batches, reducer, amp, nparams, world, rank,
     if dp:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
+    if args.dump_outputs and rank == 0:   # what train_model returns: the epoch's history (empty test loader)
+        dump_outputs(args.dump_outputs, {k: torch.tensor(h[k], dtype=torch.float64)
+                                         for k in ("train_loss", "train_dice", "train_iou")})
     if rank == 0:
         rec = {"metric": _metric(args), "value": round(args.batch * world * args.steps / el, 3), "unit": "images/sec",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3),

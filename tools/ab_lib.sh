@@ -4,7 +4,7 @@ O=gpurun_out/$1; mkdir -p $O; G=${2:-stripe_attn_fwd}
 L=$PWD/cswin-simam-unet_amd/csu/_lib
 for i in 1 2; do for v in a b; do
   if [ $v = a ]; then export CSU_LIB_PATH=$L/libcsu_hip.so; else export CSU_LIB_PATH=$L/libcsu_hip_ab.so; fi
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --cpu-baseline off --no-ref-arch > $O/bench_${v}_$i.json 2> $O/bench.err || exit 1
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --cpu-baseline off --no-ref-arch > $O/bench_${v}_$i.json 2> $O/bench.err || exit 1
   python tools/bench_summary.py $O/bench_${v}_$i.json | grep images
   python -c "
 import json;r=json.loads(open('$O/bench_${v}_$i.json').read().splitlines()[-1])

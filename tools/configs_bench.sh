@@ -6,7 +6,7 @@
 O=gpurun_out/${1:-cfgs}; mkdir -p $O
 run() {   # name, bench args...
   local n=$1; shift
-  timeout -k 10 420 python -u bench.py "$@" --no-ref-arch > $O/$n.json 2> $O/$n.err || { tail -20 $O/$n.err; exit 1; }
+  timeout -k 10 420 python -u bench.py --full "$@" --no-ref-arch > $O/$n.json 2> $O/$n.err || { tail -20 $O/$n.err; exit 1; }
   python tools/bench_summary.py $O/$n.json | grep images
 }
 run cfg1_256_fp32 --img 256 --batch 8 --dtype fp32

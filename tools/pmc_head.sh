@@ -8,7 +8,7 @@ R=$(pwd); O=$R/gpurun_out/${T:-r04d}; mkdir -p $O; export TMPDIR=/tmp
 IFS='|' read -ra LIST <<< "${CFGS:-unet:--model unet|c512:--img 512 --batch 16}"
 for cfg in "${LIST[@]}"; do
   tag=${cfg%%:*}; args=${cfg#*:}
-  timeout -k 10 300 python -u bench.py $args --steps 6 --warmup 2 --cpu-baseline off > $O/bench_$tag.json 2> $O/bench_$tag.err || { tail -20 $O/bench_$tag.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full $args --steps 6 --warmup 2 --cpu-baseline off > $O/bench_$tag.json 2> $O/bench_$tag.err || { tail -20 $O/bench_$tag.err; exit 1; }
   cd /tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/$tag/p0 -o p0 -- python3 $R/bench.py $args --steps 5 --warmup 2 --cpu-baseline off --no-roofline > $O/$tag.p0.log 2>&1 || { tail -20 $O/$tag.p0.log; exit 1; }
   cd $R

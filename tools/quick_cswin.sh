@@ -2,7 +2,7 @@
 # Headline bench (512 B16, no CPU baseline) + rocprofv3 kernel trace of the 512 CSWin step.  T=<tag>.
 set -e
 T=${T:-quick}; O=gpurun_out/$T; mkdir -p $O; R=$(pwd); export TMPDIR=/tmp
-timeout -k 10 300 python -u bench.py --cpu-baseline off > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --cpu-baseline off > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python tools/bench_summary.py $O/bench.json | head -3
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_cswin -o $T -- \
