@@ -1369,6 +1369,62 @@ def bce_loss_stats(prob: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tens
     return _BCELossFn.apply(prob, target, True)
 
 
+class _SegLossFn(torch.autograd.Function):
+    """w_bce * BCE + w_tversky * mean over rows of (1 - Tversky) on fp32 probabilities viewed as
+    rows x (n / rows) (csrc/seg_loss.hip): csu_seg_loss_fwd (one streaming pass + a fixed-order
+    finish, which also leaves two backward coefficients per row) and csu_seg_loss_bwd (one
+    elementwise pass) -- the traffic of _BCELossFn.  params = (w_bce, pos_weight, w_tversky, alpha,
+    beta, smooth).  with_stats: the same pass also returns _BCELossFn's thresholded sums as a
+    non-differentiable (3,) tensor."""
+
+    @staticmethod
+    def forward(ctx, p, t, params, rows: int, with_stats: bool = False):
+        p, t = p.contiguous(), t.contiguous()
+        n = p.numel()
+        w_bce, pos_weight, w_tv, alpha, beta, smooth = (float(v) for v in params)
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        stats = torch.empty(3, dtype=torch.float32, device=p.device) if with_stats else None
+        coef = torch.empty(rows, 2, dtype=torch.float32, device=p.device)
+        nws = lib().csu_seg_loss_workspace(n, rows)
+        ws = torch.empty(nws // 4, dtype=torch.float32, device=p.device)
+        _launch("seg_loss", lambda: lib().csu_seg_loss_fwd(n, rows, ptr(p), ptr(t), w_bce, pos_weight, w_tv, alpha, beta,
+                                                           smooth, ptr(loss), ptr(stats), ptr(coef), ptr(ws), nws,
+                                                           stream_ptr(p.device)), 16 * n, 8 * n, prec="f32")
+        ctx.save_for_backward(p, t, coef)
+        ctx.seg = (rows, w_bce, pos_weight, w_tv)
+        if with_stats:
+            ctx.mark_non_differentiable(stats)
+            return loss, stats
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        p, t, coef = ctx.saved_tensors
+        rows, w_bce, pos_weight, w_tv = ctx.seg
+        g = g.float().contiguous()
+        dp = torch.empty_like(p)
+        n = p.numel()
+        _launch("seg_loss_bwd", lambda: lib().csu_seg_loss_bwd(n, rows, ptr(p), ptr(t), ptr(g), ptr(coef), w_bce, pos_weight,
+                                                               w_tv, ptr(dp), stream_ptr(p.device)),
+                10 * n, 12 * n, prec="f32")
+        return dp, None, None, None, None
+
+
+def seg_loss(prob: torch.Tensor, target: torch.Tensor, params, rows: int, with_stats: bool = False):
+    """Fused BCE + Tversky loss of fp32 device probabilities (see _SegLossFn); params = (w_bce,
+    pos_weight, w_tversky, alpha, beta, smooth), rows divides prob.numel().  with_stats: returns
+    (loss, (sum(pred * t), sum(pred), sum(t)) of pred = prob > 0.5)."""
+    require_device(prob, target)
+    if prob.dtype != torch.float32 or target.dtype != torch.float32 or prob.shape != target.shape:
+        raise ValueError("seg_loss: fp32 probabilities and targets of one shape")
+    rows = int(rows)
+    if rows < 1 or prob.numel() < 1 or prob.numel() % rows:
+        raise ValueError("seg_loss: rows must divide the number of elements")
+    if len(params) != 6:
+        raise ValueError("seg_loss: params = (w_bce, pos_weight, w_tversky, alpha, beta, smooth)")
+    return _SegLossFn.apply(prob, target, tuple(params), rows, bool(with_stats))
+
+
 def augment_batch(images: torch.Tensor, masks: torch.Tensor, params) -> Tuple[torch.Tensor, torch.Tensor]:
     """csu_augment_batch: uint8 (B, S, S, 3) images / (B, S, S) masks on the device, params per image
     (hflip, vflip, clockwise quarter turns, top, left, crop_h, crop_w) -> fp32 (B, 3, S, S) and

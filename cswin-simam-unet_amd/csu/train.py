@@ -194,6 +194,9 @@ class _GraphedEval:
         if self.crit is bce_loss:
             loss, st = bce_loss_stats(out, self.t)
             return torch.cat([loss.detach().double().view(1), st.double()])
+        if hasattr(self.crit, "loss_stats"):     # csu.losses.SegLoss: loss + sums from one fused pass
+            loss, st = self.crit.loss_stats(out, self.t)
+            return torch.cat([loss.detach().double().view(1), st.double()])
         return _step_stats(self.crit(out, self.t), out, self.t)
 
     def __call__(self, x, t):
@@ -274,7 +277,8 @@ class _GraphedTrain:
                 g["capturable"] = True
             self.opt.sync_lr()
             self.gs = GraphedTrainStep(self.model, self.opt, self.crit, images, masks, self.dtype, warmup=0,
-                                       reducer=self.reducer, metrics=self.crit is bce_loss)
+                                       reducer=self.reducer,
+                                       metrics=self.crit is bce_loss or hasattr(self.crit, "loss_stats"))
         loss, out = self.gs(images, masks)
         if self.gs.stats is not None:
             return torch.cat([loss.double().view(1), self.gs.stats.double()])
@@ -376,8 +380,9 @@ class GraphedTrainStep:
     def __init__(self, model, optimizer, criterion, example_x, example_t, autocast_dtype=None, warmup=3,
                  reducer=None, metrics=False, capture=True):
         self.model, self.opt, self.crit = model, optimizer, criterion
-        # metrics (criterion bce_loss): the reference loop's per-step thresholded Dice / IoU sums
-        # (cswin:789-795) computed inside the graph by the loss kernel -> self.stats after a replay
+        # metrics (criterion bce_loss or one with a loss_stats method): the reference loop's per-step
+        # thresholded Dice / IoU sums (cswin:789-795) computed inside the graph by the loss kernel ->
+        # self.stats after a replay
         self.metrics = metrics
         self.stats = None
         self.reducer = reducer
@@ -446,9 +451,13 @@ class GraphedTrainStep:
         with torch.autocast("cuda", dtype=self.dtype or torch.float32, enabled=self.dtype is not None):
             out = self.model(self.x)
         if self.metrics:
-            if self.crit is not bce_loss:
-                raise ValueError("GraphedTrainStep(metrics=True) needs criterion=csu.train.bce_loss")
-            loss, self._stats = bce_loss_stats(out, self.t)
+            if self.crit is bce_loss:
+                loss, self._stats = bce_loss_stats(out, self.t)
+            elif hasattr(self.crit, "loss_stats"):
+                loss, self._stats = self.crit.loss_stats(out, self.t)
+            else:
+                raise ValueError("GraphedTrainStep(metrics=True) needs criterion=csu.train.bce_loss or one with a "
+                                 "loss_stats method (csu.losses.SegLoss)")
         else:
             loss, self._stats = self.crit(out, self.t), None
         loss.backward()

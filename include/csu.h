@@ -719,6 +719,31 @@ int csu_bce_loss_bwd(long n, const float* p, const float* t, const float* dloss,
 int csu_pack_nhwc_bf16(int B, int C, int H, int W, int Cp, const float* x, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fused segmentation loss (csrc/seg_loss.hip): BCE + Tversky (Dice is alpha = beta = 0.5) on fp32
+ * probabilities p and targets t (n elements) viewed as rows x (n / rows); rows = 1 is the
+ * batch-flattened form of the Dice metric (cswin:692-698), rows = B the per-image form.  Per row r:
+ *   TP = sum p t, P = sum p, T = sum t, D = (1 - alpha - beta) TP + alpha P + beta T + smooth,
+ *   TI = (TP + smooth) / D;
+ *   BCE = (1/n) sum -(pos_weight t max(log p, -100) + (1 - t) max(log1p(-p), -100));
+ *   loss[0] = w_bce BCE + w_tversky mean_r(1 - TI_r), deterministic (fixed-order sums, no atomics).
+ * fwd also writes coef (rows x 2 floats: A_r = (D - (TP + smooth)(1 - alpha - beta)) / D^2,
+ * C_r = alpha (TP + smooth) / D^2) for bwd and, with stats != NULL, the thresholded sums of
+ * csu_bce_loss_fwd_stats over the whole batch (stats[0] = sum(pred * t), stats[1] = sum(pred),
+ * stats[2] = sum(t), pred = p > 0.5).  Workspace csu_seg_loss_workspace(n, rows) bytes.
+ * bwd: dp = dloss[0] (w_bce (p (1 - t) - pos_weight t (1 - p)) / max(p (1 - p), 1e-12) / n
+ *                     - (w_tversky / rows) (t A_r - C_r));  at pos_weight 1 the first term is bce_loss's.
+ * CSU_E_ARG: n < 1, rows < 1, n % rows != 0, smooth <= 0, a negative weight, alpha, beta or
+ * pos_weight, or both weights zero.  Any address alignment is accepted (16-B accesses are used
+ * where p, t and dp share their offset within 16 B).
+ * ------------------------------------------------------------------------------------- */
+size_t csu_seg_loss_workspace(long n, int rows);
+int csu_seg_loss_fwd(long n, int rows, const float* p, const float* t, float w_bce, float pos_weight, float w_tversky,
+                     float alpha, float beta, float smooth, float* loss, float* stats, float* coef, void* workspace,
+                     size_t ws_bytes, void* stream);
+int csu_seg_loss_bwd(long n, int rows, const float* p, const float* t, const float* dloss, const float* coef,
+                     float w_bce, float pos_weight, float w_tversky, float* dp, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mask-aligned batch augmentation (AugmentationTransform cswin:20-87 + the dataset's /255 and
  * HWC -> CHW, cswin:166-173), square S x S images: img uint8 (B, S, S, 3), mask uint8 (B, S, S),
  * params int32 (B, 7) on the device = {hflip, vflip, clockwise quarter turns 0..3, crop top,

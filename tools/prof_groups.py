@@ -25,6 +25,7 @@ GROUPS = [("head_fold_bwd", "carafe_head_bwd"), ("head_fold_fwd", "head_fold"), 
           ("head_fwd", "head_fwd"), ("head_bwd", "head_bwd"), ("gemm_f32", "gemm"), ("slab_sum", "gemm"),
           ("dropout_apply", "dropout"), ("quant_e4m3", "quant_e4m3"), ("grad_join", "grad_join"),
           ("pack_nhwc", "pack_nhwc"), ("bce_partial", "bce_loss"), ("bce_final", "bce_loss"),
+          ("seg_partial", "seg_loss"), ("seg_finish", "seg_loss"), ("seg_backward", "seg_loss_bwd"),
           ("bce_backward", "bce_loss_bwd"), ("head_z", "carafe_head_fwd"), ("rng_advance", "dropout")]
 
 
