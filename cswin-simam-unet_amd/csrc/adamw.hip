@@ -10,23 +10,37 @@
 // Streaming kernel: 28 B per parameter (read p, g, m, v; write p, m, v), HBM-bound; + 2 B per bf16
 // shadow layout written (the forward's weight copies, csu.h), which replaces a separate cast pass
 // re-reading every fp32 weight (4 B + the same 2 B per layout).
-#include "common.hpp"
+//
+// Gradient clipping (csu_adamw_step_ex): the CLIP instantiations multiply every gradient element by
+// the device coefficient ctl[1] that csu_grad_norm_finish wrote (grad_norm.hip) while the element is
+// in registers -- no extra traffic -- and may skip the whole step when ctl[2] says the gradient
+// norm was not finite.
+#include "adamw_items.hpp"
 
 namespace csu {
 namespace {
 
-constexpr int NT = 256;
-constexpr int PER = 16;                  // elements per thread
-constexpr long CH = (long)NT * PER;      // elements per chunk (workgroup)
+using namespace adamw_items;
 
 struct AdamConst {
     float beta1, beta2, eps, wd, step_size, bc2s, decay;
+    float coef;   // CLIP: the clip coefficient every gradient element is multiplied by first
 };
 
-template <bool L2> __device__ __forceinline__ void adam4(const AdamConst& k, float* pv, const float* gv0, float* mv, float* vv) {
+// g * c rounded on its own: never contracted into the fmaf / subtraction that consumes it, so a
+// clipped step is bitwise "scale the gradient, then run the plain step" (__fmul_rn is a plain
+// product in HIP, which the compiler may fuse)
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+template <bool L2, bool CLIP>
+__device__ __forceinline__ void adam4(const AdamConst& k, float* pv, const float* gv0, float* mv, float* vv) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float g = gv0[j];
+        if constexpr (CLIP) g = mul_rn(g, k.coef);
         if constexpr (L2) g = fmaf(k.wd, pv[j], g);
         else pv[j] *= k.decay;
         mv[j] = fmaf(1.f - k.beta1, g - mv[j], mv[j]);   // lerp(m, g, 1 - beta1)
@@ -36,24 +50,7 @@ template <bool L2> __device__ __forceinline__ void adam4(const AdamConst& k, flo
     }
 }
 
-// n (<= 4) elements at index i: one 16-B vector when vec (n == 4, 16-B aligned), else scalars
-__device__ __forceinline__ void ld4n(const float* p, long i, int n, bool vec, float* v) {
-    if (vec) load4(p + i, v);
-    else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < n ? p[i + j] : 0.f;
-    }
-}
-template <typename T> __device__ __forceinline__ void st4n(T* p, long i, int n, bool vec, const float* v) {
-    if (vec) store4(p + i, v);
-    else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < n) p[i + j] = from_f<T>(v[j]);
-    }
-}
-
-template <bool L2>
+template <bool L2, bool CLIP>
 __device__ __forceinline__ void update(const AdamConst& k, float* p, const float* g, float* m, float* v, long i, int n,
                                        bool vec, float* pv) {
     float gv[4], mv[4], vv[4];
@@ -61,7 +58,7 @@ __device__ __forceinline__ void update(const AdamConst& k, float* p, const float
     ld4n(g, i, n, vec, gv);
     ld4n(m, i, n, vec, mv);
     ld4n(v, i, n, vec, vv);
-    adam4<L2>(k, pv, gv, mv, vv);
+    adam4<L2, CLIP>(k, pv, gv, mv, vv);
     st4n(p, i, n, vec, pv);
     st4n(m, i, n, vec, mv);
     st4n(v, i, n, vec, vv);
@@ -72,29 +69,33 @@ __device__ __forceinline__ void update(const AdamConst& k, float* p, const float
 // Shadow modes (csu.h): tile items update a 64 x 64 tile and write W and, through LDS, W^T in
 // bf16; flat items write the bf16 copy at the same index, conv items scatter the OHWI / IHWO
 // layouts (the csu_cast_bf16_batch layouts, now made from the updated fp32 value in registers).
-template <bool L2>
+// CLIP (csu_adamw_step_ex): ctl = the device scalars of csu_grad_norm_finish; g <- g * ctl[1] before
+// anything else (the L2 term included), and with skip != 0 and ctl[2] == 0 (non-finite gradient
+// norm) every workgroup returns before it loads or stores anything else.  ctl and skip are unused
+// without CLIP.
+template <bool L2, bool CLIP = false>
 __global__ __launch_bounds__(NT) void adamw_kernel(const csu_adamw_item* __restrict__ items, int count, const float* lr_dev,
                                                    float lr_host, float beta1, float beta2, float eps, float wd,
-                                                   const float* step_dev, float step_host) {
+                                                   const float* step_dev, float step_host, const float* ctl, int skip) {
     __shared__ bf16 tile[64][64 + 2];
-    const long b = blockIdx.x;
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {   // last item with chunk0 <= b
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].chunk0 <= b) lo = mid; else hi = mid - 1;
+    if constexpr (CLIP) {
+        if (skip && ctl[2] == 0.f) return;
     }
-    const csu_adamw_item it = items[lo];
+    const long b = blockIdx.x;
+    const csu_adamw_item it = items[find_item(items, count, b)];
     const float lr = lr_dev ? *lr_dev : lr_host;
     const float step = step_dev ? *step_dev : step_host;
+    float coef = 1.f;
+    if constexpr (CLIP) coef = ctl[1];   // read beside lr / step: its latency hides behind theirs
     const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
-    const AdamConst k{beta1, beta2, eps, wd, lr / bc1, sqrtf(bc2), L2 ? 1.f : 1.f - lr * wd};
+    const AdamConst k{beta1, beta2, eps, wd, lr / bc1, sqrtf(bc2), L2 ? 1.f : 1.f - lr * wd, coef};
     float* p = it.param;
     const float* g = it.grad;
     float* m = it.exp_avg;
     float* v = it.exp_avg_sq;
     bf16* sh = (bf16*)it.shadow;
     bf16* sht = (bf16*)it.shadow_t;
-    if (sh && sht && it.taps == 0) {   // 64 x 64 tile of a rows x cols matrix: W and W^T shadows
+    if (is_tiled(it)) {   // 64 x 64 tile of a rows x cols matrix: W and W^T shadows
         const int tk = (it.cols + 63) / 64;
         const long t = b - it.chunk0;
         const int r0 = (int)(t / tk) * 64, c0 = (int)(t % tk) * 64;
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(NT) void adamw_kernel(const csu_adamw_item* __restr
                 const int n = min(4, it.cols - c);
                 const bool vec = (it.cols & 3) == 0;   // then n == 4 and the row segment is 16-B aligned
                 const long e = (long)r * it.cols + c;
-                update<L2>(k, p, g, m, v, e, n, vec, pv);
+                update<L2, CLIP>(k, p, g, m, v, e, n, vec, pv);
                 st4n(sh, e, n, vec, pv);
             }
 #pragma unroll
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(NT) void adamw_kernel(const csu_adamw_item* __restr
         if (i >= it.numel) break;
         const int n = vec ? 4 : (int)(it.numel - i < 4 ? it.numel - i : 4);
         float pv[4];
-        update<L2>(k, p, g, m, v, i, n, vec, pv);
+        update<L2, CLIP>(k, p, g, m, v, i, n, vec, pv);
         if (!sh) continue;
         if (it.taps > 0) {   // conv weight [n][c][tap] -> OHWI [n][tap][c] (stride cols_pad), IHWO [c][tap][n]
             const unsigned TP = it.taps, CT = (unsigned)it.cols * TP;
@@ -165,7 +166,7 @@ extern "C" int csu_adamw_step(const csu_adamw_item* items, int count, long total
                               void* stream) {
     if (!items || count < 1 || total_chunks < 1) return fail(CSU_E_ARG, "adamw: empty item table");
     adamw_kernel<false><<<(unsigned)total_chunks, NT, 0, as_stream(stream)>>>(items, count, lr_dev, lr, beta1, beta2, eps,
-                                                                              weight_decay, step_dev, step);
+                                                                              weight_decay, step_dev, step, nullptr, 0);
     return check_launch("adamw");
 }
 
@@ -174,6 +175,21 @@ extern "C" int csu_adam_l2_step(const csu_adamw_item* items, int count, long tot
                                 void* stream) {
     if (!items || count < 1 || total_chunks < 1) return fail(CSU_E_ARG, "adam_l2: empty item table");
     adamw_kernel<true><<<(unsigned)total_chunks, NT, 0, as_stream(stream)>>>(items, count, lr_dev, lr, beta1, beta2, eps,
-                                                                             weight_decay, step_dev, step);
+                                                                             weight_decay, step_dev, step, nullptr, 0);
     return check_launch("adam_l2");
+}
+
+extern "C" int csu_adamw_step_ex(const csu_adamw_item* items, int count, long total_chunks, const float* lr_dev, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, const float* step_dev, float step,
+                                 const float* ctl, int skip_nonfinite, int l2, void* stream) {
+    if (!items || count < 1 || total_chunks < 1) return fail(CSU_E_ARG, "adamw_step_ex: empty item table");
+    if (!ctl) return fail(CSU_E_ARG, "adamw_step_ex: null ctl (csu_grad_norm_finish writes it)");
+    hipStream_t st = as_stream(stream);
+    if (l2)
+        adamw_kernel<true, true><<<(unsigned)total_chunks, NT, 0, st>>>(items, count, lr_dev, lr, beta1, beta2, eps,
+                                                                        weight_decay, step_dev, step, ctl, skip_nonfinite);
+    else
+        adamw_kernel<false, true><<<(unsigned)total_chunks, NT, 0, st>>>(items, count, lr_dev, lr, beta1, beta2, eps,
+                                                                         weight_decay, step_dev, step, ctl, skip_nonfinite);
+    return check_launch("adamw_step_ex");
 }

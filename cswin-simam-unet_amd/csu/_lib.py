@@ -139,6 +139,13 @@ _SIGS = {
                                       c_float, c_void_p, c_float, c_void_p]),
     "csu_adam_l2_step": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_float, c_float, c_float, c_float,
                                       c_float, c_void_p, c_float, c_void_p]),
+    "csu_grad_norm_workspace": (c_size_t, [ctypes.c_long]),
+    "csu_grad_sumsq": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_void_p]),
+    "csu_grad_norm_finish": (ctypes.c_int, [c_void_p, ctypes.c_long, c_float, c_void_p, c_void_p]),
+    "csu_grad_scale": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_void_p]),
+    "csu_adamw_step_ex": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_float, c_float, c_float,
+                                         c_float, c_float, c_void_p, c_float, c_void_p, ctypes.c_int, ctypes.c_int,
+                                         c_void_p]),
     "csu_gemm_ex": (ctypes.c_int, [ctypes.POINTER(GemmDesc), c_void_p]),
     "csu_mlp_fwd_ln": (ctypes.c_int, [ctypes.c_long, ctypes.c_int] + [c_void_p] * 8 + [c_void_p, c_void_p, c_float, c_void_p,
                                                                                c_void_p, c_void_p, c_void_p]),

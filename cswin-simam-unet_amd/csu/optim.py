@@ -9,7 +9,15 @@ Drop-in for ``torch.optim.AdamW`` (same constructor arguments, param_groups, sta
 kernel launch updates every parameter of a group from a device table of pointers.  The table is
 rebuilt only when the set of (param, grad) buffers changes, from a pinned host buffer, so the step
 can also be captured into a HIP graph (lr and the step count then live in device tensors that are
-updated in place: ``capturable=True``)."""
+updated in place: ``capturable=True``).
+
+Gradient clipping (``max_grad_norm``, ``skip_nonfinite``): the global L2 norm of all gradients of all
+param groups is reduced on the device over the same tables (csu_grad_sumsq + csu_grad_norm_finish),
+and the step kernel multiplies every gradient element by the resulting coefficient while it holds
+it in registers (csu_adamw_step_ex) -- ``torch.nn.utils.clip_grad_norm_`` + ``step()`` without a
+host sync, so it is captured with the step.  ``p.grad`` itself is left UNSCALED by this fused path
+(only the update sees the clipped value); ``csu.optim.clip_grad_norm_`` is the stand-alone,
+in-place form for other optimizers."""
 from __future__ import annotations
 
 import numpy as np
@@ -37,12 +45,33 @@ def _chunks(n, spec, chunk):
 class FusedAdamW(torch.optim.Optimizer):
     _L2 = False   # FusedAdam: coupled L2 weight decay (torch.optim.Adam)
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False,
+                 max_grad_norm=None, skip_nonfinite=False):
+        """``max_grad_norm``: clip the global L2 norm of all gradients (all param groups together, as
+        ``clip_grad_norm_(model.parameters(), max_grad_norm)``) before the update; ``skip_nonfinite``:
+        a step whose gradient norm is inf / NaN changes nothing (parameters, moments, shadows and
+        the step count keep their values; ``skipped_steps`` counts it).  Both are plain attributes,
+        not param-group entries: state_dict() keeps torch.optim.AdamW's format."""
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay:
             raise ValueError("invalid AdamW hyper-parameter")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"invalid betas {betas}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"invalid max_grad_norm {max_grad_norm} (None: no clipping)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        # device scalars of the norm pass, allocated HERE, outside any capture (see _capture_dev below):
+        # _ctl = (norm, clip coefficient, finite flag, 0) written by csu_grad_norm_finish
+        dev0 = next((p.device for g in self.param_groups for p in g["params"] if p.is_cuda), None)
+        self._ctl = self.grad_norm = self.skipped_steps = self._partial = None
+        self._retired = []
+        if dev0 is not None:
+            self._ctl = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float32, device=dev0)
+            self.grad_norm = self._ctl[0]          # pre-clip norm of the last step; same storage at every replay
+            self.skipped_steps = torch.zeros((), dtype=torch.int32, device=dev0)
+            if self._clipping():
+                self._reserve_partial(self._chunk_bound())
         self._tables = {}
         self._gstate = {}
         self._deferred = []
@@ -68,6 +97,56 @@ class FusedAdamW(torch.optim.Optimizer):
                 n = max(1, len(g["params"])) * _ITEM.itemsize
                 self._pinned[gi] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
                 self._capture_dev[gi] = torch.empty(n, dtype=torch.uint8, device=g["params"][0].device)
+        if self._ctl is not None and self._clipping():
+            self._reserve_partial(self._chunk_bound())
+
+    def _clipping(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _chunk_bound(self):
+        """Upper bound of the chunk count of all groups' tables, whichever shadow layouts the
+        parameters have by the time they step (flat chunks, or 64 x 64 tiles of [shape[0], rest])."""
+        chunk = lib().csu_adamw_chunk_elems()
+        n = 0
+        for g in self.param_groups:
+            for p in g["params"]:
+                flat = -(-p.numel() // chunk)
+                tiles = -(-p.shape[0] // 64) * -(-(p.numel() // p.shape[0]) // 64) if p.dim() >= 2 and p.numel() else 0
+                n += max(flat, tiles, 1)
+        return n
+
+    def _reserve_partial(self, chunks):
+        """The fp64 partial-sum buffer of the norm pass (one per chunk of every group's table),
+        allocated outside any capture for the same reason as the table images above."""
+        if self._partial is not None and self._partial.numel() >= chunks:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW: the gradient-norm workspace is too small for this capture (call "
+                               "prepare_capture() before capturing)")
+        if self._partial is not None and self._captured:
+            self._retired.append(self._partial)      # a captured graph keeps writing the old buffer
+        self._partial = torch.empty(max(1, chunks), dtype=torch.float64, device=self._ctl.device)
+
+    def _norm_pass(self, work):
+        """csu_grad_sumsq of every group's table into its slice of the partial buffer, then ONE
+        csu_grad_norm_finish over all of them -> self._ctl (norm, coefficient, finite flag)."""
+        total = sum(w["table"][4] for w in work)
+        self._reserve_partial(total)
+        dev = self._ctl.device
+        if any(w["dev"] != dev for w in work):
+            raise RuntimeError("FusedAdamW: gradient clipping needs every param group on one device")
+        L, off = lib(), 0
+        for w in work:
+            _, _, table, n, chunks = w["table"]
+            part = self._partial.data_ptr() + 8 * off
+            numel = sum(it[4] for it in w["items"])
+            launch("grad_norm", lambda: L.csu_grad_sumsq(table.data_ptr(), n, chunks, part, stream_ptr(dev)),
+                   0, 4 * numel, prec="f32")       # algorithmic: every gradient read once
+            off += chunks
+        mx = self.max_grad_norm if self.max_grad_norm is not None else 0.0
+        launch("grad_norm", lambda: L.csu_grad_norm_finish(self._partial.data_ptr(), total, float(mx),
+                                                           self._ctl.data_ptr(), stream_ptr(dev)),
+               0, 0, prec="f32")
 
     def _table(self, gi, items, device):
         """Device item table for the current (param, grad) buffers, rebuilt when they change
@@ -120,6 +199,8 @@ class FusedAdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         from .ops import shadow_spec, shadows_written
+        clip = self._clipping()
+        work = []
         for gi, group in enumerate(self.param_groups):
             items, dev, keep, shadowed = [], None, [], []
             for p in group["params"]:
@@ -146,6 +227,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 dev = p.device
             if not items:
                 continue
+            work.append({"gi": gi, "group": group, "items": items, "dev": dev, "keep": keep, "shadowed": shadowed})
+        if clip and work:
+            # one norm over all param groups, ordered before the step-count adds and the step kernels
+            for w in work:
+                w["table"] = self._table(w["gi"], w["items"], w["dev"])
+            self._norm_pass(work)
+            if self.skip_nonfinite:
+                self.skipped_steps += self._ctl[2] == 0
+        for w in work:
+            gi, group, items, dev, shadowed = w["gi"], w["group"], w["items"], w["dev"], w["shadowed"]
             gs = self._gstate.get(gi)
             if gs is None:
                 # one device step count per group (every parameter of a group steps together);
@@ -155,7 +246,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 step0 = float(st0) if st0 is not None else 0.0
                 gs = self._gstate[gi] = {"step": torch.full((), step0, dtype=torch.float32, device=dev),
                                          "lr": torch.full((), group["lr"], dtype=torch.float32, device=dev)}
-            gs["step"] += 1
+            if clip and self.skip_nonfinite:
+                gs["step"] += self._ctl[2]       # a skipped step does not count: + 1 only when the norm is finite
+            else:
+                gs["step"] += 1
             for p in group["params"]:
                 if p.grad is not None:
                     self.state[p]["step"] = gs["step"]
@@ -163,12 +257,16 @@ class FusedAdamW(torch.optim.Optimizer):
             lr_ptr = gs["lr"].data_ptr() if group["capturable"] else None
             b1, b2 = group["betas"]
             numel = sum(it[4] for it in items)
-            fn = lib().csu_adam_l2_step if self._L2 else lib().csu_adamw_step
+            args = (table.data_ptr(), n, chunks, lr_ptr, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                    float(group["weight_decay"]), gs["step"].data_ptr(), 0.0)
+            if clip:
+                fn = lib().csu_adamw_step_ex
+                args += (self._ctl.data_ptr(), int(self.skip_nonfinite), int(self._L2))
+            else:
+                fn = lib().csu_adam_l2_step if self._L2 else lib().csu_adamw_step
             nsh = sum(2 * it[4] * (1 + (it[5][1] != 0)) for it in items if it[5][0])
-            launch("adamw", lambda: fn(table.data_ptr(), n, chunks, lr_ptr, float(group["lr"]), float(b1),
-                                                         float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                         gs["step"].data_ptr(), 0.0, stream_ptr(dev)),
-                   12 * numel, 28 * numel + nsh, idem=False, prec="f32")
+            launch("adamw", lambda: fn(*args, stream_ptr(dev)), 12 * numel, 28 * numel + nsh, idem=False, prec="f32")
+            # (a skipped step leaves the shadows as they are: still the bf16 image of the unchanged weights)
             shadows_written(shadowed)
         return loss
 
@@ -239,5 +337,76 @@ class FusedAdam(FusedAdamW):
     moments) on the same one-launch kernel: the plain UNet's optimizer (unet:486-490)."""
     _L2 = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
+                 max_grad_norm=None, skip_nonfinite=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+
+
+def _grads_of(parameters):
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    return [p.grad for p in parameters if p.grad is not None]
+
+
+def _device_norm(grads, max_norm, scale):
+    """(norm, coef, finite, 0) device tensor of dense fp32 GPU gradients: a flat-item table of the
+    gradients (csu_adamw_item with only grad / numel / chunk0 set), csu_grad_sumsq +
+    csu_grad_norm_finish, and csu_grad_scale in place when ``scale``.  No host sync."""
+    dev = grads[0].device
+    for g in grads:
+        if g.is_sparse or g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
+            raise RuntimeError("csu.optim gradient norm: dense contiguous fp32 gradients on one GPU only")
+    L = lib()
+    chunk = L.csu_adamw_chunk_elems()
+    rec = np.zeros(len(grads), dtype=_ITEM)
+    c0 = 0
+    for i, g in enumerate(grads):
+        rec[i] = (0, g.data_ptr(), 0, 0, g.numel(), c0) + _NO_SHADOW
+        c0 += max(1, -(-g.numel() // chunk))
+    host = torch.empty(rec.nbytes, dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:] = np.frombuffer(rec.tobytes(), dtype=np.uint8)
+    table = torch.empty(rec.nbytes, dtype=torch.uint8, device=dev)
+    table.copy_(host, non_blocking=True)
+    partial = torch.empty(c0, dtype=torch.float64, device=dev)
+    ctl = torch.empty(4, dtype=torch.float32, device=dev)
+    numel = sum(g.numel() for g in grads)
+    st = stream_ptr(dev)
+    launch("grad_norm", lambda: L.csu_grad_sumsq(table.data_ptr(), len(grads), c0, partial.data_ptr(), st),
+           0, 4 * numel, prec="f32")
+    launch("grad_norm", lambda: L.csu_grad_norm_finish(partial.data_ptr(), c0, float(max_norm), ctl.data_ptr(), st),
+           0, 0, prec="f32")
+    if scale:
+        launch("grad_scale", lambda: L.csu_grad_scale(table.data_ptr(), len(grads), c0, ctl.data_ptr() + 4, st),
+               numel, 8 * numel, idem=False, prec="f32")
+    return ctl
+
+
+def grad_norm(parameters) -> torch.Tensor:
+    """Global L2 norm of the gradients of ``parameters`` (a 0-dim tensor on their device; no host
+    sync on the GPU): the value ``clip_grad_norm_`` returns, without clipping."""
+    grads = _grads_of(parameters)
+    if not grads:
+        return torch.tensor(0.0)
+    if not grads[0].is_cuda:
+        return torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in grads]))
+    return _device_norm([g if g.is_contiguous() else g.contiguous() for g in grads], 0.0, False)[0]
+
+
+def clip_grad_norm_(parameters, max_norm) -> torch.Tensor:
+    """Drop-in for ``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (L2 norm) for users with
+    another optimizer: three launches over one table of all gradients instead of ~2 small torch
+    kernels per tensor, scaling ``p.grad`` in place by min(1, max_norm / (norm + 1e-6)).  Dense fp32
+    GPU gradients; returns the total norm as a device tensor without a host sync.  Eager only
+    (FusedAdamW(max_grad_norm=...) is the form a captured step uses).  CPU gradients go to torch."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    grads = _grads_of(parameters)
+    if not grads:
+        return torch.tensor(0.0)
+    if not grads[0].is_cuda:
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm)
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"invalid max_norm {max_norm}")
+    return _device_norm(grads, max_norm, True)[0]

@@ -247,9 +247,42 @@ def train_step(model, images, masks, criterion, optimizer, reducer=None, amp_dty
     loss.backward()
     if reducer is not None:
         reducer.finish()
+    _clip_for(optimizer)
     optimizer.step()
     with torch.no_grad():
         return _step_stats(loss, outputs, masks)
+
+
+def _clip_for(optimizer):
+    """Global-norm clipping for an optimizer that carries ``max_grad_norm`` but does not clip itself
+    (make_optimizer's torch.optim.AdamW on the CPU): torch's clip_grad_norm_ over the parameters of
+    its groups, the pre-clip norm kept as ``optimizer.grad_norm``.  csu's FusedAdamW clips inside
+    step().  After a GradAllReduce every rank holds the same averaged gradients, so every rank gets
+    the same norm and takes the same decision."""
+    from .optim import FusedAdamW
+    c = getattr(optimizer, "max_grad_norm", None)
+    if c is None or isinstance(optimizer, FusedAdamW):
+        return
+    params = [p for g in optimizer.param_groups for p in g["params"]]
+    optimizer.grad_norm = torch.nn.utils.clip_grad_norm_(params, c)
+
+
+def _clip_epoch(norms, optimizer, skipped0):
+    """(mean pre-clip gradient norm over the epoch's steps with a finite norm, steps skipped this
+    epoch) from the per-step device scalars: one host sync."""
+    if not norms:
+        return 0.0, 0
+    s = torch.stack([n.double().reshape(()) for n in norms])
+    ok = torch.isfinite(s)
+    mean = torch.where(ok, s, torch.zeros_like(s)).sum() / ok.sum().clamp(min=1)
+    now = getattr(optimizer, "skipped_steps", None)
+    sk = (now - skipped0).double() if isinstance(now, torch.Tensor) and skipped0 is not None else torch.zeros_like(mean)
+    gn, sk = torch.stack([mean, sk.to(mean.device)]).tolist()
+    return float(gn), int(sk)
+
+
+def _clips(optimizer) -> bool:
+    return getattr(optimizer, "max_grad_norm", None) is not None or bool(getattr(optimizer, "skip_nonfinite", False))
 
 
 class _GraphedTrain:
@@ -299,9 +332,16 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     batch shape's step is captured into one HIP graph after two eager steps and replayed (the
     speed bench.py reports); a batch of another shape (ragged last batch) runs eagerly.  Graphs are
     kept per model across calls.  ``reducer``: a csu.dist.GradAllReduce for data-parallel training
-    (captured with the step)."""
+    (captured with the step).
+    Gradient clipping: an optimizer with ``max_grad_norm`` / ``skip_nonfinite`` (make_optimizer) adds
+    two history keys, ``grad_norm`` (per-epoch mean of the per-step pre-clip global norm over the steps
+    with a finite norm) and ``skipped_steps`` (per-epoch count of skipped non-finite steps), from
+    device scalars read once per epoch; without the options the history has the reference's keys."""
     history = {"train_loss": [], "train_dice": [], "train_iou": [], "test_loss": [], "test_dice": [], "test_iou": [],
                "learning_rates": []}
+    clips = _clips(optimizer)
+    if clips:
+        history["grad_norm"], history["skipped_steps"] = [], []
     rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
     start = 0
     if resume_from is not None:
@@ -323,7 +363,9 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
         it = train_loader
         if verbose and rank0 and tqdm is not None:
             it = tqdm(train_loader, desc=f"Epoch {epoch + 1}/{num_epochs} [TRAIN]")
-        stats = []
+        stats, norms = [], []
+        skipped0 = getattr(optimizer, "skipped_steps", None)
+        skipped0 = skipped0.clone() if isinstance(skipped0, torch.Tensor) else None
         for images, masks in it:
             images = images.to(device, non_blocking=True)
             masks = masks.to(device, non_blocking=True)
@@ -336,7 +378,13 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
                 stats.append(g(images, masks))
             else:
                 stats.append(train_step(model, images, masks, criterion, optimizer, reducer, amp_dtype=amp_dtype))
+            if clips and isinstance(getattr(optimizer, "grad_norm", None), torch.Tensor):
+                norms.append(optimizer.grad_norm.detach().clone())   # the optimizer rewrites it in place
         train_loss, train_dice, train_iou = _epoch_means(stats)
+        if clips:
+            gn, sk = _clip_epoch(norms, optimizer, skipped0)
+            history["grad_norm"].append(gn)
+            history["skipped_steps"].append(sk)
         test_loss, test_dice, test_iou = evaluate_model(model, test_loader, criterion, device, amp_dtype=amp_dtype,
                                                         graph=use_graph)
         if scheduler is not None:
@@ -357,14 +405,25 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     return history
 
 
-def make_optimizer(model, lr=1e-4, weight_decay=1e-4, capturable=False):
+def make_optimizer(model, lr=1e-4, weight_decay=1e-4, capturable=False, max_grad_norm=None, skip_nonfinite=False):
     """AdamW as in cswin:937-941.  On the GPU: csu.optim.FusedAdamW (one csu_adamw_step launch for
     all 463 tensors; ``capturable=True`` reads lr/step from device tensors so the step can live in a
-    HIP graph); on the CPU: torch.optim.AdamW."""
+    HIP graph); on the CPU: torch.optim.AdamW.
+    ``max_grad_norm`` (not in the reference): clip the global L2 gradient norm before every update --
+    fused into FusedAdamW's step on the GPU; on the CPU the value is set as ``opt.max_grad_norm`` and
+    train_step calls torch's clip_grad_norm_.  ``skip_nonfinite``: skip a step whose gradient norm
+    is inf / NaN (GPU only)."""
+    if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+        raise ValueError(f"invalid max_grad_norm {max_grad_norm} (None: no clipping)")
     if next(model.parameters()).is_cuda:
         from .optim import FusedAdamW
-        return FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=capturable)
-    return torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+        return FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=capturable,
+                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    if skip_nonfinite:
+        raise ValueError("make_optimizer(skip_nonfinite=True) needs csu.optim.FusedAdamW (a model on the GPU)")
+    opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+    opt.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+    return opt
 
 
 class GraphedTrainStep:
@@ -463,6 +522,7 @@ class GraphedTrainStep:
         loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
+        _clip_for(self.opt)      # FusedAdamW: nothing here, its step() clips (captured with it)
         self.opt.step()
         return loss.detach(), out.detach()
 

@@ -519,6 +519,41 @@ int csu_adam_l2_step(const csu_adamw_item* items, int count, long total_chunks, 
                      void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Global-norm gradient clipping over a csu_adamw_item table (the optimizer's own: same items, same
+ * chunk numbering, only `grad`, numel, chunk0 and the tile fields are read), with no host sync.
+ * Sums are fp64 from the element on and in a fixed order (no atomics): equal gradients give a
+ * bitwise equal norm.
+ *
+ * csu_grad_sumsq: partial[chunk] = sum g^2 over the in-bounds elements of every chunk
+ *   (total_chunks doubles, csu_grad_norm_workspace bytes).  Replaces the per-tensor
+ *   torch.linalg.vector_norm / torch._foreach_norm launches of torch.nn.utils.clip_grad_norm_
+ *   (get_total_norm).
+ * csu_grad_norm_finish: one workgroup sums n partials (of one or several tables laid side by side)
+ *   and writes the device scalars
+ *     ctl[0] = norm = (float)sqrt(sum)
+ *     ctl[1] = coef = min(1, max_norm / (norm + 1e-6))   (exactly 1 when nothing is clipped;
+ *              max_norm <= 0 or infinite: 1, norm-only mode; a NaN norm gives NaN as in torch)
+ *     ctl[2] = 1 if the sum is finite, else 0
+ *     ctl[3] = 0.
+ *   Replaces the stack + vector_norm of the per-tensor norms and the clamp(max_norm / (norm + 1e-6))
+ *   of clip_grad_norm_ (clip_grads_with_norm_).
+ * csu_grad_scale: g *= *coef_dev in place for every item.  Replaces clip_grad_norm_'s
+ *   torch._foreach_mul_(grads, clip_coef) (for optimizers other than csu's).
+ * csu_adamw_step_ex: csu_adamw_step (l2 == 0) / csu_adam_l2_step (l2 != 0) on g * ctl[1], the product
+ *   rounded on its own before anything else uses it: bitwise equal to csu_grad_scale followed by the
+ *   plain step, without touching the gradients in memory.  skip_nonfinite != 0 and ctl[2] == 0: the
+ *   launch changes nothing (params, moments and shadows keep their values).  Replaces
+ *   _foreach_mul_ + the fused AdamW launches, and a GradScaler-style found-inf skip.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_grad_norm_workspace(long total_chunks);
+int csu_grad_sumsq(const csu_adamw_item* items, int count, long total_chunks, double* partial, void* stream);
+int csu_grad_norm_finish(const double* partial, long n, float max_norm, float* ctl, void* stream);
+int csu_grad_scale(const csu_adamw_item* items, int count, long total_chunks, const float* coef_dev, void* stream);
+int csu_adamw_step_ex(const csu_adamw_item* items, int count, long total_chunks, const float* lr_dev, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, const float* step_dev, float step,
+                      const float* ctl, int skip_nonfinite, int l2, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Dropout / DropPath (nn.Dropout cswin:190/193/512, timm DropPath cswin:344/367-368) as one
  * elementwise pass where no producing kernel fuses it:
  *   out[i] = res[i] + row_scale[(i / cols) / rows_per_sample] * keep(site, i) / (1 - p) * x[i]
