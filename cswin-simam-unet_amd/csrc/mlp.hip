@@ -4,6 +4,7 @@
 //   backward  h  = fc1(x) (recomputed), g = gelu(h)
 //             dH = (dY W2) * gelu'(h),  dX = dH W1             (the two input-gradient GEMMs + GELU')
 //             writes dH and g for the weight-gradient GEMMs dW1 = dH^T x, dW2 = dY^T g
+//             (C = 64, mlp_bwd64_wgrad: forms dW1 / db1 / dW2 / db2 itself, dH and g stay on chip)
 //
 // The unfused form moves the hidden layer (M x 4C bf16) through HBM three times in the forward
 // (h and gelu(h) written, gelu(h) read) and three more in the backward; here the forward reads x
@@ -681,6 +682,219 @@ int persist_grid(long M) {   // one workgroup (two panel streams) per CU, fewer 
     }
     const long pan = (M + BM - 1) / BM;
     return (int)(pan < 2L * cus ? (pan + 1) / 2 : cus);
+}
+
+// s <- fl(s + v), returns the rounding error of that add (Knuth's two-sum: exact for any magnitudes)
+__device__ __forceinline__ float two_sum(float& s, float v) {
+    const float t = s + v;
+    const float bb = t - s;
+    const float e = (s - (t - bb)) + (v - bb);
+    s = t;
+    return e;
+}
+
+// mlp_bwd64_wgrad's grid: at least two workgroups (one without panels writes a zero partial), because
+// csu_wslab_reduce_batch treats a one-chunk item as already written to its destination
+int wgrad_grid(long M) {
+    const int g = persist_grid(M);
+    return g < 2 ? 2 : g;
+}
+
+// mlp_bwd64_persist that also forms the weight and bias gradients, so g and dH never reach HBM.  The
+// dX arithmetic of a panel is that kernel's, instruction for instruction (two teams of 4 waves, one
+// 64-token panel each per iteration).  Per hidden chunk the 8 waves write their bf16 g / dH values
+// (the values the other kernel stores) into [128 tokens][64 hidden] LDS images beside the iteration's
+// x / dY images, and after a barrier every wave adds one 32x32 tile of the chunk's
+//     dW1[64 j + .][.] += dH_chunk^T x   (waves 0-3)      dW2[.][64 j + .] += dY^T g_chunk   (waves 4-7)
+// over the 128 tokens (8 MFMAs, both operands by transposing reads of the token-major images: the
+// contraction runs over tokens).  The 4 tiles per wave (one per chunk, 64 accumulator registers) live
+// for the whole launch; db1 / db2 are per-lane sums of the dH / dY A fragments (lane = feature).  At
+// the end each workgroup writes one partial in wslab_sum's layout (32x32 tiles, chunk = workgroup):
+// csu_wslab_reduce_batch adds the partials in workgroup order -- no atomics, bitwise reproducible.
+// Tokens past M have x = dY = 0, hence dH = 0 and no contribution.
+// LDS: 64 KB weights + 64 KB token images + 1 KB b1; the dX exchange aliases the g / dH images.
+template <bool DROP>
+__global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __restrict__ X, const bf16* __restrict__ dY,
+                                                          const bf16* __restrict__ W1, const float* __restrict__ b1,
+                                                          const bf16* __restrict__ W2, bf16* __restrict__ dX,
+                                                          float* __restrict__ slab1, float* __restrict__ slab2, MlpDrop dd) {
+    constexpr int C = 64, NCH = 4 * C / HC, KS = C / 16, TF = C / 32, IMG = HC * C;
+    constexpr int PT = 2 * BM;            // tokens per iteration (both teams)
+    constexpr int TIMG = PT * 64;         // one token-major image: [PT][64 features], 128-B rows
+    // DROP: x / dY fragments are re-read from their images per chunk instead of held in registers
+    // (32 of them; the mask arithmetic would otherwise spill at two waves per SIMD)
+    constexpr bool XLDS = DROP;
+    using D1 = Dma<HC, 2 * C, 8>;
+    using D2 = Dma<C, 2 * HC, 8>;
+    __shared__ __attribute__((aligned(1024))) bf16 wimg[2 * NCH * IMG];
+    __shared__ __attribute__((aligned(1024))) bf16 timg[4 * TIMG];
+    __shared__ __attribute__((aligned(16))) float b1s[4 * C];
+    bf16* const ximg = timg;
+    bf16* const dyimg = timg + TIMG;
+    bf16* const gimg = timg + 2 * TIMG;
+    bf16* const dhimg = timg + 3 * TIMG;
+    static_assert(2 * TIMG * sizeof(bf16) >= 2 * 4 * (C / 64) * 16 * 64 * sizeof(float), "dX exchange must fit the g / dH images");
+    const int lane = threadIdx.x & 63;
+    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int team = wave8 >> 2, wave = wave8 & 3;
+    const int r = lane & 31, h = lane >> 5;
+    const int t = wave >> 1, u = wave & 1;
+    const int tok = 32 * t + r;
+    const int hs = 32 * u;
+    const int trow = BM * team + tok;     // this lane's token row in the images
+    // weight-gradient role: team 0 -> dW1 tile (hidden 32 t .., c 32 u ..), team 1 -> dW2 tile (c 32 u .., hidden 32 t ..)
+    const bf16* const aimg = team ? dyimg : dhimg;
+    const bf16* const bimg = team ? gimg : ximg;
+    const int a0 = team ? 32 * u : 32 * t;
+    const int bo = team ? 32 * t : 32 * u;
+    const bool bias_all = team == 0 && u == 0;   // db1 of hidden 64 j + 32 t + (lane & 31), every chunk
+    const bool bias_one = team == 1 && t == 0;   // db2 of c 32 u + (lane & 31), once per iteration
+    for (int i = threadIdx.x; i < 4 * C; i += 2 * MT) b1s[i] = b1[i];
+    {
+        D1 d1;
+        D2 d2;
+        d1.init(C, wave8, lane);
+        d2.init(4 * C, wave8, lane);
+        const i32x4 rs_w1 = rsrc4(W1, 4L * C * C * 2);
+        const i32x4 rs_w2 = rsrc4(W2, 4L * C * C * 2);
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            dma<D1::NW>(rs_w1, d1.v, (unsigned)j * HC * C * 2, wimg + j * IMG, wave8);
+            dma<D2::NW>(rs_w2, d2.v, (unsigned)j * HC * 2, wimg + (NCH + j) * IMG, wave8);
+        }
+        vmwait<0>();
+        lds_sync();
+    }
+    const long npan = (M + BM - 1) / BM;
+    const long mine = blockIdx.x < npan ? (npan - 1 - blockIdx.x) / gridDim.x + 1 : 0;
+    const long iters = (mine + 1) / 2;
+    DropoutRng Rh;
+    if constexpr (DROP) Rh = load_rng(dd.rng, dd.site_h, dd.p);
+    float* xc = reinterpret_cast<float*>(gimg) + team * (4 * (C / 64) * 16 * 64);
+    f32x16 wacc[NCH];
+    float bsum[NCH], bcmp[NCH];   // bias sums, compensated (a lane adds ~1000 tokens per launch)
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        wacc[j] = f32x16{};
+        bsum[j] = bcmp[j] = 0.f;
+    }
+    for (long it = 0; it < iters; ++it) {
+        const long k = 2 * it + team;
+        const long m0 = (blockIdx.x + k * (long)gridDim.x) * BM;
+        const long rows = k < mine ? M - m0 : 0;
+        const long mb = rows > 0 ? m0 : 0;
+        const bool ok = tok < rows;
+        bf16x8 xf[KS], dyf[KS];
+        load_bfrags<C>(buf_rsrc(X + mb * C, rows * C * 2), tok, ok, h, xf);
+        load_bfrags<C>(buf_rsrc(dY + mb * C, rows * C * 2), tok, ok, h, dyf);
+        // the iteration's x / dY images; the last barrier of the previous iteration is behind every
+        // read of them.  Waves u = 0 / 1 of a token half hold the same rows: without XLDS one writes x
+        // and the other dY; with it both write both (the same bytes) and read back only their own
+        // writes, so GEMM1 / GEMM3 need no barrier.
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int o = moff<128>(trow, 16 * s + 8 * h);
+            if constexpr (XLDS) {
+                *reinterpret_cast<bf16x8*>(ximg + o) = xf[s];
+                *reinterpret_cast<bf16x8*>(dyimg + o) = dyf[s];
+            } else {
+                *reinterpret_cast<bf16x8*>((u ? dyimg : ximg) + o) = u ? dyf[s] : xf[s];
+            }
+        }
+        const long mg = m0 + tok;
+        f32x16 acc[TF];
+#pragma unroll
+        for (int i = 0; i < TF; ++i) acc[i] = f32x16{};
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const bf16* w1c = wimg + j * IMG;
+            const bf16* w2c = wimg + (NCH + j) * IMG;
+            f32x16 ha = f32x16{}, ga = f32x16{};
+#pragma unroll
+            for (int s2 = 0; s2 < KS; ++s2) {
+                const int o = moff<128>(trow, 16 * s2 + 8 * h);
+                const bf16x8 xs = XLDS ? frag(ximg, o) : xf[s2];
+                const bf16x8 ds = XLDS ? frag(dyimg, o) : dyf[s2];
+                ha = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(w1c, moff<2 * C>(hs + r, 16 * s2 + 8 * h)), xs, ha, 0, 0, 0);
+                ga = __builtin_amdgcn_mfma_f32_32x32x16_bf16(trfrag<2 * HC>(w2c, hs, s2, lane), ds, ga, 0, 0, 0);
+            }
+            float bv[16], gv[16], dv[16];
+            bias16(b1s, j * HC + hs, h, bv);
+            unsigned km = 0xffffu;
+            if constexpr (DROP) if (dd.p > 0.f) km = keep16_crow(Rh, ((uint64_t)mg * 4 * C + j * HC + hs) >> 3, h);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                float dg;
+                gelu_pair_fast(ha[e] + bv[e], gv[e], dg);
+                if constexpr (DROP) {
+                    const float ms = ((km >> e) & 1u) ? Rh.scale : 0.f;
+                    gv[e] *= ms;
+                    dg *= ms;
+                }
+                dv[e] = ga[e] * dg;
+            }
+            // bf16 g / dH of this lane's token: features hs + 8 g + 4 h .. + 3 (every wave is past the
+            // previous chunk's image reads: the barrier that closed it)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int o = moff<128>(trow, hs + 8 * g + 4 * h);
+                store4(gimg + o, gv + 4 * g);
+                store4(dhimg + o, dv + 4 * g);
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const bf16x8 db = pack_b(dv, s2);
+#pragma unroll
+                for (int ft = 0; ft < TF; ++ft)
+                    acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ptrfrag<2 * C>(w1c, 32 * ft, hs + 16 * s2, lane), db, acc[ft], 0, 0, 0);
+            }
+            lds_sync();   // the chunk's g / dH (and, at j = 0, x / dY) images are complete
+            const bool dob = bias_all || (bias_one && j == 0);
+#pragma unroll
+            for (int s = 0; s < PT / 16; ++s) {
+                const bf16x8 fa = trfrag<128>(aimg, a0, s, lane);
+                const bf16x8 fb = trfrag<128>(bimg, bo, s, lane);
+                wacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, wacc[j], 0, 0, 0);
+                if (dob && team) {   // db2, once per iteration: every add compensated
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) bcmp[j] += two_sum(bsum[j], (float)fa[i]);
+                } else if (dob) {    // db1, every chunk: pairwise within the fragment (8 bf16 values mostly add
+                                     // exactly), then one two-sum -- the kernel is VALU-bound
+                    const float v = (((float)fa[0] + (float)fa[1]) + ((float)fa[2] + (float)fa[3]))
+                                    + (((float)fa[4] + (float)fa[5]) + ((float)fa[6] + (float)fa[7]));
+                    bcmp[j] += two_sum(bsum[j], v);
+                }
+            }
+            lds_sync();   // image reads done: the next chunk (or the dX exchange below) may overwrite
+        }
+        const auto rs_dx = buf_rsrc(dX + mb * C, rows * C * 2);
+        if (u == 0) {
+            exchange_half<C, 0>(acc, xc, wave, lane);
+            bwd_epilogue<C, 0>(acc, rs_dx, tok, ok, h);
+        } else {
+            exchange_half<C, 1>(acc, xc, wave, lane);
+            bwd_epilogue<C, 1>(acc, rs_dx, tok, ok, h);
+        }
+        lds_sync();
+    }
+    // partials: slab[tile][workgroup][32 x 32], then the bias rows [n tile][workgroup][32]
+    const long G = gridDim.x, wg = blockIdx.x;
+    float* const slab = team ? slab2 : slab1;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int ht = 2 * j + t;                              // 32-hidden tile of the 256
+        const long tile = team ? u * (4 * C / 32) + ht : ht * (C / 32) + u;
+        float* p = slab + (tile * G + wg) * 1024 + r;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) p[crow(e, h) * 32] = wacc[j][e];
+        // the two token halves of the k-steps: both lanes form the same sum (fixed operand order)
+        const float so = __shfl_xor(bsum[j], 32, 64), co = __shfl_xor(bcmp[j], 32, 64);
+        float bs = h ? so : bsum[j];
+        const float be = two_sum(bs, h ? bsum[j] : so);
+        bs += be + ((h ? co : bcmp[j]) + (h ? bcmp[j] : co));
+        const bool wb = team ? (t == 0 && j == 0) : u == 0;
+        if (wb && h == 0) slab[16L * G * 1024 + ((team ? u : ht) * G + wg) * 32 + r] = bs;
+    }
 }
 
 // ================================================================================================
@@ -2121,6 +2335,42 @@ extern "C" int csu_mlp_bwd_dp(long M, int C, const void* x, const void* dy, cons
 extern "C" int csu_mlp_bwd(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
                            void* dh, void* g, void* dx, void* stream) {
     return csu_mlp_bwd_dp(M, C, x, dy, w1, b1, w2, dh, g, dx, nullptr, stream);
+}
+
+extern "C" int csu_mlp_bwd_wgrad_supported(int C) { return C == 64; }
+
+// fp32 partials per workgroup: dW (4C x C or C x 4C, 32x32 tiles) + the bias rows
+extern "C" int csu_mlp_bwd_wgrad_workspace(long M, int C, size_t* slab1_bytes, size_t* slab2_bytes) {
+    if (M < 1 || !csu_mlp_bwd_wgrad_supported(C) || !slab1_bytes || !slab2_bytes)
+        return fail(CSU_E_ARG, "mlp_bwd_wgrad_workspace: bad arguments (C must be 64)");
+    const size_t g = (size_t)wgrad_grid(M);
+    *slab1_bytes = g * (4 * C * C + 4 * C) * sizeof(float);
+    *slab2_bytes = g * (4 * C * C + C) * sizeof(float);
+    return 0;
+}
+
+extern "C" int csu_mlp_bwd_wgrad(long M, int C, const void* x, const void* dy, const void* w1, const float* b1,
+                                 const void* w2, void* dx, const csu_mlp_dropout* d, float* slab1, float* slab2,
+                                 csu_wslab_item* item1, csu_wslab_item* item2, float* dw1_db1, float* dw2_db2,
+                                 void* stream) {
+    if (M < 1 || !x || !dy || !w1 || !b1 || !w2 || !dx || !slab1 || !slab2 || !item1 || !item2 || !dw1_db1 || !dw2_db2)
+        return fail(CSU_E_ARG, "mlp_bwd_wgrad: bad arguments");
+    if (!csu_mlp_bwd_wgrad_supported(C)) return fail(CSU_E_ARG, "mlp_bwd_wgrad: C must be 64");
+    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_bwd_wgrad: tensor exceeds 2 GB buffer range");
+    MlpDrop md{};
+    const int e = mlp_drop_of(d, md);
+    if (e < 0) return e;
+    const int grid = wgrad_grid(M);
+    const hipStream_t st = as_stream(stream);
+    if (d && e == 0)
+        mlp_bwd64_wgrad<true><<<dim3((unsigned)grid), 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
+                                                                       (const bf16*)w2, (bf16*)dx, slab1, slab2, md);
+    else
+        mlp_bwd64_wgrad<false><<<dim3((unsigned)grid), 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
+                                                                        (const bf16*)w2, (bf16*)dx, slab1, slab2, MlpDrop{});
+    *item1 = csu_wslab_item{slab1, dw1_db1, 4 * C, C, 32, 32, grid, 0};
+    *item2 = csu_wslab_item{slab2, dw2_db2, C, 4 * C, 32, 32, grid, 0};
+    return check_launch("mlp_bwd_wgrad");
 }
 
 extern "C" int csu_mlp_fp8_supported(int C) { return C == 64 || C == 128 || C == 256; }

@@ -233,6 +233,13 @@ _SIGS = {
                                       c_void_p, ctypes.POINTER(MlpDropout), c_void_p]),
     "csu_mlp_bwd_dp": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, ctypes.POINTER(MlpDropout), c_void_p]),
+    "csu_mlp_bwd_wgrad_supported": (ctypes.c_int, [ctypes.c_int]),
+    "csu_mlp_bwd_wgrad_workspace": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.POINTER(c_size_t),
+                                                   ctypes.POINTER(c_size_t)]),
+    "csu_mlp_bwd_wgrad": (ctypes.c_int, [ctypes.c_long, ctypes.c_int] + [c_void_p] * 6 + [ctypes.POINTER(MlpDropout), c_void_p,
+                                                                                          c_void_p, ctypes.POINTER(WslabItem),
+                                                                                          ctypes.POINTER(WslabItem), c_void_p,
+                                                                                          c_void_p, c_void_p]),
     "csu_mlp_bwd": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
     "csu_conv2d_fwd": (ctypes.c_int, [ctypes.POINTER(ConvGeom), ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1707,6 +1707,52 @@ def _mlp_desc(drop: Optional[MlpDrop], rpi: int):
     return d
 
 
+# Stage 1 (C = 64): the fused backward also forms dW1 / db1 / dW2 / db2 (csu_mlp_bwd_wgrad), so dh and g are
+# neither allocated nor written; its per-workgroup partials join the end-of-backward slab sums.
+# False: the two-step path (csu_mlp_bwd_dp + two weight-gradient items), for A/B runs and tests.
+MLP64_FUSED_WGRAD = os.environ.get("CSU_MLP64_FUSED_WGRAD", "1") != "0"
+
+
+def _mlp_bwd_wgrad(M, C, x2, dyb, w1c, b1f, w2c, dx, dd, dts, params):
+    """The fused Mlp backward with in-kernel weight gradients when the library has it for C and both
+    [dW | db] pairs may be deferred; returns (dw1, db1, dw2, db2) -- filled by the end-of-backward
+    flush -- or None (the caller runs the two-step path)."""
+    w1dt, b1dt, w2dt, b2dt = dts
+    if not (MLP64_FUSED_WGRAD and DEFER_WGRAD and GROUP_WGRAD and lib().csu_mlp_bwd_wgrad_supported(C)):
+        return None
+    if x2.dtype != torch.bfloat16 or any(p is None for p in params) or None in dts:
+        return None
+    p1, p2 = params[:2], params[2:]
+    if _side_ok(dyb, w1dt, b1dt, params=p1) or _side_ok(dyb, w2dt, b2dt, params=p2):
+        return None   # eager side-stream mode keeps the weight gradients off the main stream
+    if not (_wgrad_deferrable(dyb, w1dt, b1dt, p1) and _wgrad_deferrable(dyb, w2dt, b2dt, p2)):
+        return None
+    L = lib()
+    dev = x2.device
+    n1, n2 = ctypes.c_size_t(), ctypes.c_size_t()
+    check(L.csu_mlp_bwd_wgrad_workspace(M, C, ctypes.byref(n1), ctypes.byref(n2)), "mlp_bwd_wgrad_workspace")
+    slab1 = torch.empty(n1.value // 4, dtype=torch.float32, device=dev)
+    slab2 = torch.empty(n2.value // 4, dtype=torch.float32, device=dev)
+    out1, out2 = _grad_dest(p1), _grad_dest(p2)
+    if out1 is None:
+        out1 = torch.empty(4 * C * C + 4 * C, dtype=torch.float32, device=dev)
+    if out2 is None:
+        out2 = torch.empty(4 * C * C + C, dtype=torch.float32, device=dev)
+    it1, it2 = _lib.WslabItem(), _lib.WslabItem()
+    _launch("mlp_bwd", lambda: L.csu_mlp_bwd_wgrad(M, C, ptr(x2), ptr(dyb), ptr(w1c), ptr(b1f), ptr(w2c), ptr(dx), dd,
+                                                   ptr(slab1), ptr(slab2), ctypes.byref(it1), ctypes.byref(it2), ptr(out1),
+                                                   ptr(out2), stream_ptr(dev)),
+            24 * M * C * C + 16 * M * C * C, M * C * 6 + 16 * C * C + n1.value + n2.value)
+    _WG_PENDING.append((it1, out1, slab1))   # keeps the slabs and the results alive until the sums ran
+    _WG_PENDING.append((it2, out2, slab2))
+    _queue_flush()
+    r1 = (out1[:4 * C * C].view(4 * C, C), out1[4 * C * C:])
+    r2 = (out2[:4 * C * C].view(C, 4 * C), out2[4 * C * C:])
+    _late(p2, r2)
+    _late(p1, r1)
+    return r1 + r2
+
+
 class _MlpFusedFn(torch.autograd.Function):
     """res + fc2(gelu(fc1(x))) (Mlp cswin:180-196 + residual cswin:368) in ONE csu_mlp_fwd launch
     (the 4C hidden layer never reaches HBM).  Backward: one csu_mlp_bwd launch recomputes h and
@@ -1759,10 +1805,15 @@ class _MlpFusedFn(torch.autograd.Function):
             dyb = _bf16_of(dy).view(-1, C)
         else:
             dyb = drop.out_grad(dy.reshape(-1, C).contiguous(), torch.bfloat16)
-        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
-        g = torch.empty_like(dh)
         dx = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
         dd = ctypes.byref(_mlp_desc(drop, ctx.rpi))
+        fused = _mlp_bwd_wgrad(M, C, x2, dyb, w1c, b1f, w2c, dx, dd, (w1dt, b1dt, w2dt, b2dt), ctx.params)
+        if fused is not None:
+            dw1, db1, dw2, db2 = fused
+            return (dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None,
+                    None, None)
+        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
+        g = torch.empty_like(dh)
         _launch("mlp_bwd", lambda: lib().csu_mlp_bwd_dp(M, C, ptr(x2), ptr(dyb), ptr(w1c), ptr(b1f), ptr(w2c), ptr(dh),
                                                         ptr(g), ptr(dx), dd, stream_ptr(x2.device)),
                 24 * M * C * C, M * C * (2 + 2 + 2) + M * 4 * C * (2 + 2) + 16 * C * C)
@@ -1869,10 +1920,16 @@ class _MlpFp8Fn(torch.autograd.Function):
         else:
             dyb = drop.out_grad(dy.reshape(-1, C).contiguous(), torch.bfloat16)
         dyb = dyb.contiguous()
-        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
-        g = torch.empty_like(dh)
         dx = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
         dd = ctypes.byref(_mlp_desc(drop, ctx.rpi))
+        if C not in FP8_MLP_BWD_C:
+            fused = _mlp_bwd_wgrad(M, C, x2, dyb, ctx.wc[0], b1f, ctx.wc[1], dx, dd, (w1dt, b1dt, w2dt, b2dt), ctx.params)
+            if fused is not None:
+                dw1, db1, dw2, db2 = fused
+                return (dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None,
+                        None, None, None)
+        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
+        g = torch.empty_like(dh)
         if C in FP8_MLP_BWD_C:
             _launch("mlp_bwd", lambda: lib().csu_mlp_fp8_bwd(M, C, ptr(x2), ptr(dyb), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2t),
                                                              ptr(sw2), ptr(w1tp), ptr(dh), ptr(g), ptr(dx), dd,

@@ -617,6 +617,19 @@ int csu_mlp_fwd_dp(long M, int C, const void* x, const void* w1, const float* b1
                    const float* res, float* out, const csu_mlp_dropout* d, void* stream);
 int csu_mlp_bwd_dp(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
                    void* dh, void* g, void* dx, const csu_mlp_dropout* d, void* stream);
+/* csu_mlp_bwd_dp that also forms the weight and bias gradients, so dh and g are never written
+ * (C = 64 only: csu_mlp_bwd_wgrad_supported).  dx is bitwise csu_mlp_bwd_dp's.  Every workgroup of the
+ * persistent launch accumulates dW1 = dh^T x, db1 = colsum(dh), dW2 = dy^T g, db2 = colsum(dy) over its
+ * token panels, from the same bf16-rounded dh / g values csu_mlp_bwd_dp stores, and writes one fp32
+ * partial into slab1 ([dW1 | db1]) and slab2 ([dW2 | db2]) (sizes: csu_mlp_bwd_wgrad_workspace).  The
+ * call fills item1 / item2; csu_wslab_reduce_batch over them (any time later on the same stream, with
+ * other items) sums the partials in a fixed order into dw1_db1 (4C*C + 4C fp32: dW1 (4C, C) then db1)
+ * and dw2_db2 (C*4C + C fp32: dW2 (C, 4C) then db2).  Bitwise reproducible; no atomics. */
+int csu_mlp_bwd_wgrad_supported(int C);
+int csu_mlp_bwd_wgrad_workspace(long M, int C, size_t* slab1_bytes, size_t* slab2_bytes);
+int csu_mlp_bwd_wgrad(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
+                      void* dx, const csu_mlp_dropout* d, float* slab1, float* slab2, csu_wslab_item* item1,
+                      csu_wslab_item* item2, float* dw1_db1, float* dw2_db2, void* stream);
 /* csu_mlp_fwd_dp that also applies the NEXT CSWinBlock's norm1 LayerNorm (cswin:357) to its output
  * out (M, C) fp32 in the same launch: ln_out (M, C) bf16 = LN(out) * ln_gamma + ln_beta (eps
  * ln_eps), ln_mean / ln_rstd (M) fp32 as csu_layernorm_fwd writes them.  out must not alias res. */
