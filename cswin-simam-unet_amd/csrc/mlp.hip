@@ -4,7 +4,7 @@
 //   backward  h  = fc1(x) (recomputed), g = gelu(h)
 //             dH = (dY W2) * gelu'(h),  dX = dH W1             (the two input-gradient GEMMs + GELU')
 //             writes dH and g for the weight-gradient GEMMs dW1 = dH^T x, dW2 = dY^T g
-//             (C = 64, mlp_bwd64_wgrad: forms dW1 / db1 / dW2 / db2 itself, dH and g stay on chip)
+//             (C = 64: mlp_bwd64, which with WGRAD forms dW1 / db1 / dW2 / db2 itself, dH and g stay on chip)
 //
 // The unfused form moves the hidden layer (M x 4C bf16) through HBM three times in the forward
 // (h and gelu(h) written, gelu(h) read) and three more in the backward; here the forward reads x
@@ -33,6 +33,8 @@
 #include "rng.hpp"
 
 #include <cstdlib>
+#include <initializer_list>
+#include <string>
 #include <type_traits>
 
 namespace csu {
@@ -241,6 +243,10 @@ __device__ __forceinline__ void bias16(const float* b1s, int base, int h, float*
 
 template <bool V> using bconst = std::integral_constant<bool, V>;
 template <int V> using iconst = std::integral_constant<int, V>;
+// a launcher's runtime flag (dropout, LN) as a template argument: f(bconst<v>{})
+template <class F> void with_flag(bool v, F&& f) {
+    if (v) f(bconst<true>{}); else f(bconst<false>{});
+}
 
 // Forward.  Rings: W1 chunks in 2 stages, W2 chunks in 2 stages.  Step j (after one barrier):
 // DMA W1(j+2), W2(j+1); GEMM1(j+1) on the MFMA pipe while GELU(j) runs on the VALU; GEMM2(j).
@@ -559,120 +565,6 @@ __global__ __launch_bounds__(MT) void mlp_bwd_kernel(long M, const bf16* __restr
 }
 
 
-// Persistent backward for C = 64 (stage 1): W1 / W2 (2 x 256 x 64 bf16 = 64 KB) stay in LDS for the
-// workgroup's lifetime -- the per-panel kernel above re-stages them for every 64-token panel (4096
-// panels at 512x512 B16: 268 MB of L2 -> LDS traffic for 67 MB of token operands).  Two teams of 4
-// waves (2 waves per SIMD) run their own panel streams through the same weight images; wave (t, u)
-// of a team has the roles of the per-panel kernel; natural chunk order.  (The forward in this form
-// measured slower than the per-panel kernel: its per-chunk work is too short to hide the token
-// loads without the DMA ring's overlap.)
-template <bool DROP>
-__global__ __launch_bounds__(2 * MT) void mlp_bwd64_persist(long M, const bf16* __restrict__ X, const bf16* __restrict__ dY,
-                                                            const bf16* __restrict__ W1, const float* __restrict__ b1,
-                                                            const bf16* __restrict__ W2, bf16* __restrict__ dH,
-                                                            bf16* __restrict__ G, bf16* __restrict__ dX, MlpDrop dd) {
-    constexpr int C = 64, NCH = 4 * C / HC, KS = C / 16, TF = C / 32, IMG = HC * C;
-    using D1 = Dma<HC, 2 * C, 8>;
-    using D2 = Dma<C, 2 * HC, 8>;
-    __shared__ __attribute__((aligned(1024))) bf16 wimg[2 * NCH * IMG];
-    __shared__ __attribute__((aligned(16))) float b1s[4 * C];
-    __shared__ __attribute__((aligned(16))) float xch[2][4 * (C / 64) * 16 * 64];
-    const int lane = threadIdx.x & 63;
-    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int team = wave8 >> 2, wave = wave8 & 3;
-    const int r = lane & 31, h = lane >> 5;
-    const int t = wave >> 1, u = wave & 1;
-    const int tok = 32 * t + r;
-    const int hs = 32 * u;
-    for (int i = threadIdx.x; i < 4 * C; i += 2 * MT) b1s[i] = b1[i];
-    {
-        D1 d1;
-        D2 d2;
-        d1.init(C, wave8, lane);
-        d2.init(4 * C, wave8, lane);
-        const i32x4 rs_w1 = rsrc4(W1, 4L * C * C * 2);
-        const i32x4 rs_w2 = rsrc4(W2, 4L * C * C * 2);
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            dma<D1::NW>(rs_w1, d1.v, (unsigned)j * HC * C * 2, wimg + j * IMG, wave8);
-            dma<D2::NW>(rs_w2, d2.v, (unsigned)j * HC * 2, wimg + (NCH + j) * IMG, wave8);
-        }
-        vmwait<0>();
-        lds_sync();
-    }
-    const long npan = (M + BM - 1) / BM;
-    const long mine = blockIdx.x < npan ? (npan - 1 - blockIdx.x) / gridDim.x + 1 : 0;
-    const long iters = (mine + 1) / 2;
-    DropoutRng Rh;
-    if constexpr (DROP) Rh = load_rng(dd.rng, dd.site_h, dd.p);
-    float* xc = xch[team];
-    for (long it = 0; it < iters; ++it) {
-        const long k = 2 * it + team;
-        const long m0 = (blockIdx.x + k * (long)gridDim.x) * BM;
-        const long rows = k < mine ? M - m0 : 0;
-        const long mb = rows > 0 ? m0 : 0;
-        const bool ok = tok < rows;
-        bf16x8 xf[KS], dyf[KS];
-        load_bfrags<C>(buf_rsrc(X + mb * C, rows * C * 2), tok, ok, h, xf);
-        load_bfrags<C>(buf_rsrc(dY + mb * C, rows * C * 2), tok, ok, h, dyf);
-        const auto rs_dh = buf_rsrc(dH + mb * 4 * C, rows * 4 * C * 2);
-        const auto rs_g = buf_rsrc(G + mb * 4 * C, rows * 4 * C * 2);
-        const long mg = m0 + tok;
-        f32x16 acc[TF];
-#pragma unroll
-        for (int i = 0; i < TF; ++i) acc[i] = f32x16{};
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            const bf16* w1c = wimg + j * IMG;
-            const bf16* w2c = wimg + (NCH + j) * IMG;
-            f32x16 ha = f32x16{}, ga = f32x16{};
-#pragma unroll
-            for (int s2 = 0; s2 < KS; ++s2) {
-                ha = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(w1c, moff<2 * C>(hs + r, 16 * s2 + 8 * h)), xf[s2], ha, 0, 0, 0);
-                ga = __builtin_amdgcn_mfma_f32_32x32x16_bf16(trfrag<2 * HC>(w2c, hs, s2, lane), dyf[s2], ga, 0, 0, 0);
-            }
-            float bv[16], gv[16], dv[16];
-            bias16(b1s, j * HC + hs, h, bv);
-            unsigned km = 0xffffu;
-            if constexpr (DROP) if (dd.p > 0.f) km = keep16_crow(Rh, ((uint64_t)mg * 4 * C + j * HC + hs) >> 3, h);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float dg;
-                gelu_pair_fast(ha[e] + bv[e], gv[e], dg);
-                if constexpr (DROP) {
-                    const float ms = ((km >> e) & 1u) ? Rh.scale : 0.f;
-                    gv[e] *= ms;
-                    dg *= ms;
-                }
-                dv[e] = ga[e] * dg;
-            }
-            const unsigned base = ok ? (unsigned)(tok * 4 * C + j * HC + hs + 4 * h) * 2 : kOOB;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const unsigned o = base == kOOB ? kOOB : base + 16 * g;
-                buf_st4bf(rs_g, o, gv + 4 * g);
-                buf_st4bf(rs_dh, o, dv + 4 * g);
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 db = pack_b(dv, s2);
-#pragma unroll
-                for (int ft = 0; ft < TF; ++ft)
-                    acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ptrfrag<2 * C>(w1c, 32 * ft, hs + 16 * s2, lane), db, acc[ft], 0, 0, 0);
-            }
-        }
-        const auto rs_dx = buf_rsrc(dX + mb * C, rows * C * 2);
-        if (u == 0) {
-            exchange_half<C, 0>(acc, xc, wave, lane);
-            bwd_epilogue<C, 0>(acc, rs_dx, tok, ok, h);
-        } else {
-            exchange_half<C, 1>(acc, xc, wave, lane);
-            bwd_epilogue<C, 1>(acc, rs_dx, tok, ok, h);
-        }
-        lds_sync();
-    }
-}
-
 int persist_grid(long M) {   // one workgroup (two panel streams) per CU, fewer for small M
     static int cus = 0;
     if (!cus) {
@@ -693,18 +585,27 @@ __device__ __forceinline__ float two_sum(float& s, float v) {
     return e;
 }
 
-// mlp_bwd64_wgrad's grid: at least two workgroups (one without panels writes a zero partial), because
+// mlp_bwd64<DROP, WGRAD = true>'s grid: at least two workgroups (one without panels writes a zero partial), because
 // csu_wslab_reduce_batch treats a one-chunk item as already written to its destination
 int wgrad_grid(long M) {
     const int g = persist_grid(M);
     return g < 2 ? 2 : g;
 }
 
-// mlp_bwd64_persist that also forms the weight and bias gradients, so g and dH never reach HBM.  The
-// dX arithmetic of a panel is that kernel's, instruction for instruction (two teams of 4 waves, one
-// 64-token panel each per iteration).  Per hidden chunk the 8 waves write their bf16 g / dH values
-// (the values the other kernel stores) into [128 tokens][64 hidden] LDS images beside the iteration's
-// x / dY images, and after a barrier every wave adds one 32x32 tile of the chunk's
+// Persistent backward for C = 64 (stage 1): W1 / W2 (2 x 256 x 64 bf16 = 64 KB) stay in LDS for the
+// workgroup's lifetime -- the per-panel kernel above re-stages them for every 64-token panel (4096
+// panels at 512x512 B16: 268 MB of L2 -> LDS traffic for 67 MB of token operands).  Two teams of 4
+// waves (2 waves per SIMD) run their own panel streams through the same weight images, one 64-token
+// panel each per iteration; wave (t, u) of a team has the roles of the per-panel kernel; natural chunk
+// order.  (The forward in this form measured slower than the per-panel kernel: its per-chunk work is
+// too short to hide the token loads without the DMA ring's overlap.)
+// Without WGRAD (csu_mlp_bwd_dp) g and dH go to HBM for the weight-gradient GEMMs.
+// LDS: 64 KB weights + 32 KB dX exchange + 1 KB b1.
+//
+// WGRAD (csu_mlp_bwd_wgrad) also forms the weight and bias gradients, so g and dH never reach HBM; the
+// dX arithmetic of a panel is the same code.  Per hidden chunk the 8 waves write their bf16 g / dH
+// values (the values the other mode stores) into [128 tokens][64 hidden] LDS images beside the
+// iteration's x / dY images, and after a barrier every wave adds one 32x32 tile of the chunk's
 //     dW1[64 j + .][.] += dH_chunk^T x   (waves 0-3)      dW2[.][64 j + .] += dY^T g_chunk   (waves 4-7)
 // over the 128 tokens (8 MFMAs, both operands by transposing reads of the token-major images: the
 // contraction runs over tokens).  The 4 tiles per wave (one per chunk, 64 accumulator registers) live
@@ -713,27 +614,29 @@ int wgrad_grid(long M) {
 // csu_wslab_reduce_batch adds the partials in workgroup order -- no atomics, bitwise reproducible.
 // Tokens past M have x = dY = 0, hence dH = 0 and no contribution.
 // LDS: 64 KB weights + 64 KB token images + 1 KB b1; the dX exchange aliases the g / dH images.
-template <bool DROP>
-__global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __restrict__ X, const bf16* __restrict__ dY,
-                                                          const bf16* __restrict__ W1, const float* __restrict__ b1,
-                                                          const bf16* __restrict__ W2, bf16* __restrict__ dX,
-                                                          float* __restrict__ slab1, float* __restrict__ slab2, MlpDrop dd) {
+template <bool DROP, bool WGRAD>
+__global__ __launch_bounds__(2 * MT) void mlp_bwd64(long M, const bf16* __restrict__ X, const bf16* __restrict__ dY,
+                                                    const bf16* __restrict__ W1, const float* __restrict__ b1,
+                                                    const bf16* __restrict__ W2, bf16* __restrict__ dH, bf16* __restrict__ G,
+                                                    bf16* __restrict__ dX, float* __restrict__ slab1,
+                                                    float* __restrict__ slab2, MlpDrop dd) {
     constexpr int C = 64, NCH = 4 * C / HC, KS = C / 16, TF = C / 32, IMG = HC * C;
     constexpr int PT = 2 * BM;            // tokens per iteration (both teams)
     constexpr int TIMG = PT * 64;         // one token-major image: [PT][64 features], 128-B rows
-    // DROP: x / dY fragments are re-read from their images per chunk instead of held in registers
-    // (32 of them; the mask arithmetic would otherwise spill at two waves per SIMD)
-    constexpr bool XLDS = DROP;
+    constexpr int XCH = 4 * (C / 64) * 16 * 64;   // floats of one team's dX exchange
+    // WGRAD with DROP: x / dY fragments are re-read from their images per chunk instead of held in
+    // registers (32 of them; the mask arithmetic would otherwise spill at two waves per SIMD)
+    constexpr bool XLDS = DROP && WGRAD;
     using D1 = Dma<HC, 2 * C, 8>;
     using D2 = Dma<C, 2 * HC, 8>;
     __shared__ __attribute__((aligned(1024))) bf16 wimg[2 * NCH * IMG];
-    __shared__ __attribute__((aligned(1024))) bf16 timg[4 * TIMG];
+    __shared__ __attribute__((aligned(1024))) bf16 timg[(WGRAD ? 4 : 2) * TIMG];   // x | dY | g | dH, or the exchange alone
     __shared__ __attribute__((aligned(16))) float b1s[4 * C];
     bf16* const ximg = timg;
     bf16* const dyimg = timg + TIMG;
-    bf16* const gimg = timg + 2 * TIMG;
-    bf16* const dhimg = timg + 3 * TIMG;
-    static_assert(2 * TIMG * sizeof(bf16) >= 2 * 4 * (C / 64) * 16 * 64 * sizeof(float), "dX exchange must fit the g / dH images");
+    bf16* const gimg = timg + (WGRAD ? 2 : 0) * TIMG;
+    bf16* const dhimg = gimg + TIMG;
+    static_assert(2 * TIMG * sizeof(bf16) >= 2 * XCH * sizeof(float), "dX exchange must fit the g / dH images");
     const int lane = threadIdx.x & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int team = wave8 >> 2, wave = wave8 & 3;
@@ -770,13 +673,15 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __
     const long iters = (mine + 1) / 2;
     DropoutRng Rh;
     if constexpr (DROP) Rh = load_rng(dd.rng, dd.site_h, dd.p);
-    float* xc = reinterpret_cast<float*>(gimg) + team * (4 * (C / 64) * 16 * 64);
-    f32x16 wacc[NCH];
+    float* xc = reinterpret_cast<float*>(gimg) + team * XCH;
+    f32x16 wacc[NCH];             // WGRAD: the wave's dW tiles, one per chunk
     float bsum[NCH], bcmp[NCH];   // bias sums, compensated (a lane adds ~1000 tokens per launch)
+    if constexpr (WGRAD) {
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        wacc[j] = f32x16{};
-        bsum[j] = bcmp[j] = 0.f;
+        for (int j = 0; j < NCH; ++j) {
+            wacc[j] = f32x16{};
+            bsum[j] = bcmp[j] = 0.f;
+        }
     }
     for (long it = 0; it < iters; ++it) {
         const long k = 2 * it + team;
@@ -791,16 +696,20 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __
         // read of them.  Waves u = 0 / 1 of a token half hold the same rows: without XLDS one writes x
         // and the other dY; with it both write both (the same bytes) and read back only their own
         // writes, so GEMM1 / GEMM3 need no barrier.
+        if constexpr (WGRAD) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int o = moff<128>(trow, 16 * s + 8 * h);
-            if constexpr (XLDS) {
-                *reinterpret_cast<bf16x8*>(ximg + o) = xf[s];
-                *reinterpret_cast<bf16x8*>(dyimg + o) = dyf[s];
-            } else {
-                *reinterpret_cast<bf16x8*>((u ? dyimg : ximg) + o) = u ? dyf[s] : xf[s];
+            for (int s = 0; s < KS; ++s) {
+                const int o = moff<128>(trow, 16 * s + 8 * h);
+                if constexpr (XLDS) {
+                    *reinterpret_cast<bf16x8*>(ximg + o) = xf[s];
+                    *reinterpret_cast<bf16x8*>(dyimg + o) = dyf[s];
+                } else {
+                    *reinterpret_cast<bf16x8*>((u ? dyimg : ximg) + o) = u ? dyf[s] : xf[s];
+                }
             }
         }
+        const auto rs_dh = buf_rsrc(dH + mb * 4 * C, rows * 4 * C * 2);   // !WGRAD
+        const auto rs_g = buf_rsrc(G + mb * 4 * C, rows * 4 * C * 2);
         const long mg = m0 + tok;
         f32x16 acc[TF];
 #pragma unroll
@@ -833,13 +742,23 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __
                 }
                 dv[e] = ga[e] * dg;
             }
-            // bf16 g / dH of this lane's token: features hs + 8 g + 4 h .. + 3 (every wave is past the
-            // previous chunk's image reads: the barrier that closed it)
+            if constexpr (WGRAD) {
+                // bf16 g / dH of this lane's token: features hs + 8 g + 4 h .. + 3 (every wave is past the
+                // previous chunk's image reads: the barrier that closed it)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int o = moff<128>(trow, hs + 8 * g + 4 * h);
-                store4(gimg + o, gv + 4 * g);
-                store4(dhimg + o, dv + 4 * g);
+                for (int g = 0; g < 4; ++g) {
+                    const int o = moff<128>(trow, hs + 8 * g + 4 * h);
+                    store4(gimg + o, gv + 4 * g);
+                    store4(dhimg + o, dv + 4 * g);
+                }
+            } else {
+                const unsigned base = ok ? (unsigned)(tok * 4 * C + j * HC + hs + 4 * h) * 2 : kOOB;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const unsigned o = base == kOOB ? kOOB : base + 16 * g;
+                    buf_st4bf(rs_g, o, gv + 4 * g);
+                    buf_st4bf(rs_dh, o, dv + 4 * g);
+                }
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -848,24 +767,26 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __
                 for (int ft = 0; ft < TF; ++ft)
                     acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ptrfrag<2 * C>(w1c, 32 * ft, hs + 16 * s2, lane), db, acc[ft], 0, 0, 0);
             }
-            lds_sync();   // the chunk's g / dH (and, at j = 0, x / dY) images are complete
-            const bool dob = bias_all || (bias_one && j == 0);
+            if constexpr (WGRAD) {
+                lds_sync();   // the chunk's g / dH (and, at j = 0, x / dY) images are complete
+                const bool dob = bias_all || (bias_one && j == 0);
 #pragma unroll
-            for (int s = 0; s < PT / 16; ++s) {
-                const bf16x8 fa = trfrag<128>(aimg, a0, s, lane);
-                const bf16x8 fb = trfrag<128>(bimg, bo, s, lane);
-                wacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, wacc[j], 0, 0, 0);
-                if (dob && team) {   // db2, once per iteration: every add compensated
+                for (int s = 0; s < PT / 16; ++s) {
+                    const bf16x8 fa = trfrag<128>(aimg, a0, s, lane);
+                    const bf16x8 fb = trfrag<128>(bimg, bo, s, lane);
+                    wacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, wacc[j], 0, 0, 0);
+                    if (dob && team) {   // db2, once per iteration: every add compensated
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) bcmp[j] += two_sum(bsum[j], (float)fa[i]);
-                } else if (dob) {    // db1, every chunk: pairwise within the fragment (8 bf16 values mostly add
-                                     // exactly), then one two-sum -- the kernel is VALU-bound
-                    const float v = (((float)fa[0] + (float)fa[1]) + ((float)fa[2] + (float)fa[3]))
-                                    + (((float)fa[4] + (float)fa[5]) + ((float)fa[6] + (float)fa[7]));
-                    bcmp[j] += two_sum(bsum[j], v);
+                        for (int i = 0; i < 8; ++i) bcmp[j] += two_sum(bsum[j], (float)fa[i]);
+                    } else if (dob) {    // db1, every chunk: pairwise within the fragment (8 bf16 values mostly add
+                                         // exactly), then one two-sum -- the kernel is VALU-bound
+                        const float v = (((float)fa[0] + (float)fa[1]) + ((float)fa[2] + (float)fa[3]))
+                                        + (((float)fa[4] + (float)fa[5]) + ((float)fa[6] + (float)fa[7]));
+                        bcmp[j] += two_sum(bsum[j], v);
+                    }
                 }
+                lds_sync();   // image reads done: the next chunk (or the dX exchange below) may overwrite
             }
-            lds_sync();   // image reads done: the next chunk (or the dX exchange below) may overwrite
         }
         const auto rs_dx = buf_rsrc(dX + mb * C, rows * C * 2);
         if (u == 0) {
@@ -877,23 +798,25 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd64_wgrad(long M, const bf16* __
         }
         lds_sync();
     }
-    // partials: slab[tile][workgroup][32 x 32], then the bias rows [n tile][workgroup][32]
-    const long G = gridDim.x, wg = blockIdx.x;
-    float* const slab = team ? slab2 : slab1;
+    if constexpr (WGRAD) {
+        // partials: slab[tile][workgroup][32 x 32], then the bias rows [n tile][workgroup][32]
+        const long ng = gridDim.x, wg = blockIdx.x;
+        float* const slab = team ? slab2 : slab1;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ht = 2 * j + t;                              // 32-hidden tile of the 256
-        const long tile = team ? u * (4 * C / 32) + ht : ht * (C / 32) + u;
-        float* p = slab + (tile * G + wg) * 1024 + r;
+        for (int j = 0; j < NCH; ++j) {
+            const int ht = 2 * j + t;                              // 32-hidden tile of the 256
+            const long tile = team ? u * (4 * C / 32) + ht : ht * (C / 32) + u;
+            float* p = slab + (tile * ng + wg) * 1024 + r;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) p[crow(e, h) * 32] = wacc[j][e];
-        // the two token halves of the k-steps: both lanes form the same sum (fixed operand order)
-        const float so = __shfl_xor(bsum[j], 32, 64), co = __shfl_xor(bcmp[j], 32, 64);
-        float bs = h ? so : bsum[j];
-        const float be = two_sum(bs, h ? bsum[j] : so);
-        bs += be + ((h ? co : bcmp[j]) + (h ? bcmp[j] : co));
-        const bool wb = team ? (t == 0 && j == 0) : u == 0;
-        if (wb && h == 0) slab[16L * G * 1024 + ((team ? u : ht) * G + wg) * 32 + r] = bs;
+            for (int e = 0; e < 16; ++e) p[crow(e, h) * 32] = wacc[j][e];
+            // the two token halves of the k-steps: both lanes form the same sum (fixed operand order)
+            const float so = __shfl_xor(bsum[j], 32, 64), co = __shfl_xor(bcmp[j], 32, 64);
+            float bs = h ? so : bsum[j];
+            const float be = two_sum(bs, h ? bsum[j] : so);
+            bs += be + ((h ? co : bcmp[j]) + (h ? bcmp[j] : co));
+            const bool wb = team ? (t == 0 && j == 0) : u == 0;
+            if (wb && h == 0) slab[16L * ng * 1024 + ((team ? u : ht) * ng + wg) * 32 + r] = bs;
+        }
     }
 }
 
@@ -1328,68 +1251,51 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd8_kernel(long M, const bf16* __
     }
 }
 
+// The launchers take d = nullptr for "no dropout" (the DROP = false kernels) and ln = nullptr for "no LN".
 template <int C>
 int fwd_launch(long M, const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const float* res,
                float* out, const MlpDrop* d, long rpi, hipStream_t st, const MlpLn* ln = nullptr) {
     const dim3 grid((unsigned)((M + BM - 1) / BM));
-    if constexpr (C == 256) {
-        if (!d) {   // two waves per SIMD (dropout launches keep the 4-wave kernel)
-            if (ln)
-                mlp_fwd8_kernel<C, true, kFwd8Hc><<<grid, 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2,
-                                                                   res, out, rpi, *ln);
-            else
-                mlp_fwd8_kernel<C, false, kFwd8Hc><<<grid, 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2,
-                                                                    res, out, rpi, MlpLn{});
-            return check_launch(ln ? "mlp_fwd_ln" : "mlp_fwd");
-        }
-    }
-    if (ln) {
-        if (d)
-            mlp_fwd_kernel<C, true, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2,
-                                                                      res, out, *d, rpi, *ln);
-        else
-            mlp_fwd_kernel<C, false, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2,
-                                                                       b2, res, out, MlpDrop{}, rpi, *ln);
-        return check_launch("mlp_fwd_ln");
-    }
-    if (d)
-        mlp_fwd_kernel<C, true, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2, res,
-                                                                   out, *d, rpi);
-    else
-        mlp_fwd_kernel<C, false, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2,
-                                                                    res, out, MlpDrop{}, rpi);
-    return check_launch("mlp_fwd");
+    const auto X = (const bf16*)x, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    const MlpLn l = ln ? *ln : MlpLn{};
+    with_flag(ln != nullptr, [&](auto lnf) {
+        constexpr bool LN = decltype(lnf)::value;
+        if constexpr (C == 256)
+            if (!d) {   // two waves per SIMD (dropout launches keep the 4-wave kernel)
+                mlp_fwd8_kernel<C, LN, kFwd8Hc><<<grid, 2 * MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, rpi, l);
+                return;
+            }
+        with_flag(d != nullptr, [&](auto df) {
+            mlp_fwd_kernel<C, decltype(df)::value, LN><<<grid, MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, dd, rpi, l);
+        });
+    });
+    return check_launch(ln ? "mlp_fwd_ln" : "mlp_fwd");
 }
 
 template <int C>
 int bwd_launch(long M, const void* x, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
                void* dx, const MlpDrop* d, long rpi, hipStream_t st) {
     const dim3 grid((unsigned)((M + BM - 1) / BM));
-    if constexpr (C == 256) {
+    const auto X = (const bf16*)x, dY = (const bf16*)dy, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
+    const auto dH = (bf16*)dh, G = (bf16*)g, dX = (bf16*)dx;
+    if constexpr (C == 256)
         if (!d) {   // two waves per SIMD (dropout launches keep the 4-wave kernel)
-            mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                        (bf16*)dh, (bf16*)g, (bf16*)dx, rpi);
+            mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi);
             return check_launch("mlp_bwd");
         }
-    }
-    if constexpr (C == 64) {   // persistent, weights resident (mlp_bwd64_persist)
-        const dim3 pg((unsigned)persist_grid(M));
-        if (d)
-            mlp_bwd64_persist<true><<<pg, 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                           (bf16*)dh, (bf16*)g, (bf16*)dx, *d);
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    with_flag(d != nullptr, [&](auto df) {
+        constexpr bool D = decltype(df)::value;
+        if constexpr (C == 64)   // persistent, weights resident
+            mlp_bwd64<D, false><<<dim3((unsigned)persist_grid(M)), 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, nullptr,
+                                                                                    nullptr, dd);
         else
-            mlp_bwd64_persist<false><<<pg, 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                            (bf16*)dh, (bf16*)g, (bf16*)dx, MlpDrop{});
-        return check_launch("mlp_bwd");
-    }
-    if (d)
-        mlp_bwd_kernel<C, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                     (bf16*)dh, (bf16*)g, (bf16*)dx, *d, rpi);
-    else
-        mlp_bwd_kernel<C, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                      (bf16*)dh, (bf16*)g, (bf16*)dx, MlpDrop{}, rpi);
+            mlp_bwd_kernel<C, D><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
+    });
     return check_launch("mlp_bwd");
 }
+
 
 
 // ================================================================================================
@@ -1664,23 +1570,17 @@ int fp8_fwd_launch(long M, const void* x, const void* w1, const float* sw1, cons
                    const float* b2, const float* res, float* out, const MlpDrop* d, long rpi, hipStream_t st,
                    const MlpLn* ln = nullptr) {
     const dim3 grid((unsigned)((M + BM - 1) / BM));
-    if (ln) {
-        if (d)
-            mlp_fp8_fwd_kernel<C, true, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const uint8_t*)w1, sw1, b1,
-                                                                   (const uint8_t*)w2p, sw2, b2, res, out, *d, rpi, *ln);
-        else
-            mlp_fp8_fwd_kernel<C, false, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const uint8_t*)w1, sw1, b1,
-                                                                    (const uint8_t*)w2p, sw2, b2, res, out, MlpDrop{}, rpi, *ln);
-        return check_launch("mlp_fp8_fwd_ln");
-    }
-    if (d)
-        mlp_fp8_fwd_kernel<C, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const uint8_t*)w1, sw1, b1, (const uint8_t*)w2p,
-                                                         sw2, b2, res, out, *d, rpi);
-    else
-        mlp_fp8_fwd_kernel<C, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const uint8_t*)w1, sw1, b1, (const uint8_t*)w2p,
-                                                          sw2, b2, res, out, MlpDrop{}, rpi);
-    return check_launch("mlp_fp8_fwd");
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    const MlpLn l = ln ? *ln : MlpLn{};
+    with_flag(ln != nullptr, [&](auto lnf) {
+        with_flag(d != nullptr, [&](auto df) {
+            mlp_fp8_fwd_kernel<C, decltype(df)::value, decltype(lnf)::value><<<grid, MT, 0, st>>>(
+                M, (const bf16*)x, (const uint8_t*)w1, sw1, b1, (const uint8_t*)w2p, sw2, b2, res, out, dd, rpi, l);
+        });
+    });
+    return check_launch(ln ? "mlp_fp8_fwd_ln" : "mlp_fp8_fwd");
 }
+
 
 
 // the 32 values of a packed e4m3 operand lane: bytes [0, 16) times 2^e0, [16, 32) times 2^e1
@@ -1901,16 +1801,15 @@ template <int C>
 int fp8_bwd_launch(long M, const void* x, const void* dy, const void* w1, const float* sw1, const float* b1, const void* w2t,
                    const float* sw2, const void* w1tp, void* dh, void* g, void* dx, const MlpDrop* d, long rpi, hipStream_t st) {
     const dim3 grid((unsigned)((M + BM - 1) / BM));
-    if (d)
-        mlp_fp8_bwd_kernel<C, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const uint8_t*)w1, sw1, b1,
-                                                         (const uint8_t*)w2t, sw2, (const uint8_t*)w1tp, (bf16*)dh, (bf16*)g,
-                                                         (bf16*)dx, *d, rpi);
-    else
-        mlp_fp8_bwd_kernel<C, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const uint8_t*)w1, sw1, b1,
-                                                          (const uint8_t*)w2t, sw2, (const uint8_t*)w1tp, (bf16*)dh, (bf16*)g,
-                                                          (bf16*)dx, MlpDrop{}, rpi);
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    with_flag(d != nullptr, [&](auto df) {
+        mlp_fp8_bwd_kernel<C, decltype(df)::value><<<grid, MT, 0, st>>>(
+            M, (const bf16*)x, (const bf16*)dy, (const uint8_t*)w1, sw1, b1, (const uint8_t*)w2t, sw2, (const uint8_t*)w1tp,
+            (bf16*)dh, (bf16*)g, (bf16*)dx, dd, rpi);
+    });
     return check_launch("mlp_fp8_bwd");
 }
+
 
 
 // ================================================================================================
@@ -2070,13 +1969,14 @@ template <int C, int RS>
 int fwd_deep_launch(long M, const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const float* res,
                     float* out, const MlpDrop* d, long rpi, hipStream_t st) {
     const dim3 grid((unsigned)((M + BM - 1) / BM));
-    if (d)
-        mlp_fwd_deep<C, RS, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2, res, out, *d, rpi);
-    else
-        mlp_fwd_deep<C, RS, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2, res, out,
-                                                        MlpDrop{}, rpi);
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    with_flag(d != nullptr, [&](auto df) {
+        mlp_fwd_deep<C, RS, decltype(df)::value><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2,
+                                                                      res, out, dd, rpi);
+    });
     return check_launch("mlp_fwd (deep)");
 }
+
 
 
 // 16x16x32 operand fragments transposed out of a moff<RB> image whose ROWS are k and COLUMNS are i
@@ -2242,12 +2142,11 @@ template <int C, int RS>
 int bwd_deep_launch(long M, const void* x, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
                     void* dx, const MlpDrop* d, long rpi, hipStream_t st) {
     const dim3 grid((unsigned)((M + BM - 1) / BM));
-    if (d)
-        mlp_bwd_deep<C, RS, true><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                       (bf16*)dh, (bf16*)g, (bf16*)dx, *d, rpi);
-    else
-        mlp_bwd_deep<C, RS, false><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2,
-                                                        (bf16*)dh, (bf16*)g, (bf16*)dx, MlpDrop{}, rpi);
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    with_flag(d != nullptr, [&](auto df) {
+        mlp_bwd_deep<C, RS, decltype(df)::value><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
+                                                                      (const bf16*)w2, (bf16*)dh, (bf16*)g, (bf16*)dx, dd, rpi);
+    });
     return check_launch("mlp_bwd (deep)");
 }
 
@@ -2266,45 +2165,67 @@ static int mlp_drop_of(const csu_mlp_dropout* d, MlpDrop& md) {
     return d->p > 0.f || d->row_scale ? 0 : 1;   // 1: nothing to apply -> the dropout-free kernel
 }
 
+// What an entry point's launch needs besides its pointers
+struct MlpArgs {
+    MlpDrop md{};
+    const MlpDrop* dp = nullptr;   // null: nothing to apply -> the dropout-free kernel
+    long rpi = 0;                  // rows per image: the hidden-chunk rotation
+    hipStream_t st = nullptr;
+};
+
+// The entry points' common prologue: M >= 1, every pointer of `ptrs` non-null, the hidden layer within
+// the 2 GB buffer range, a valid dropout descriptor.  0 and `a` filled, or the error code (`name`
+// prefixes the message).
+static int mlp_args(const char* name, std::initializer_list<const void*> ptrs, long M, int C, const csu_mlp_dropout* d,
+                    void* stream, MlpArgs& a) {
+    bool ok = M >= 1;
+    for (const void* p : ptrs) ok = ok && p;
+    if (!ok) return fail(CSU_E_ARG, std::string(name) + ": bad arguments");
+    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, std::string(name) + ": tensor exceeds 2 GB buffer range");
+    const int e = mlp_drop_of(d, a.md);
+    if (e < 0) return e;
+    a.dp = d && e == 0 ? &a.md : nullptr;
+    a.rpi = d ? (long)d->rows_per_sample : 0;
+    a.st = as_stream(stream);
+    return 0;
+}
+
+// f(iconst<C>{}) for the three widths, else `code` ("<name>: C must be 64, 128 or 256")
+template <class F>
+static int dispatch_c(const char* name, int C, int code, F&& f) {
+    switch (C) {
+        case 64: return f(iconst<64>{});
+        case 128: return f(iconst<128>{});
+        case 256: return f(iconst<256>{});
+        default: return fail(code, std::string(name) + ": C must be 64, 128 or 256");
+    }
+}
+
+// ring stages of the deep-ring kernels (csu_mlp_*_ex cfg 1, or cfg 2 = DEEPER)
+template <int C, bool DEEPER> constexpr int kDeepRs = DEEPER ? (C == 64 ? 8 : C == 128 ? 6 : 3) : (C == 64 ? 6 : 4);
+
 extern "C" int csu_mlp_fwd_dp(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                               const float* res, float* out, const csu_mlp_dropout* d, void* stream) {
-    if (M < 1 || !x || !w1 || !b1 || !w2 || !b2 || !res || !out) return fail(CSU_E_ARG, "mlp_fwd: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_fwd: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;   // rows per image: the hidden-chunk rotation
-    const hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 64: return fwd_launch<64>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-        case 128: return fwd_launch<128>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-        case 256: return fwd_launch<256>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-        default: return fail(CSU_E_ARG, "mlp_fwd: C must be 64, 128 or 256");
-    }
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_fwd", {x, w1, b1, w2, b2, res, out}, M, C, d, stream, a)) return e;
+    return dispatch_c("mlp_fwd", C, CSU_E_ARG, [&](auto c) {
+        return fwd_launch<decltype(c)::value>(M, x, w1, b1, w2, b2, res, out, a.dp, a.rpi, a.st);
+    });
 }
 
 extern "C" int csu_mlp_fwd_ln(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                               const float* res, float* out, const csu_mlp_dropout* d, const float* ln_gamma,
                               const float* ln_beta, float ln_eps, void* ln_out, float* ln_mean, float* ln_rstd,
                               void* stream) {
-    if (M < 1 || !x || !w1 || !b1 || !w2 || !b2 || !res || !out || !ln_gamma || !ln_beta || !ln_out || !ln_mean || !ln_rstd)
-        return fail(CSU_E_ARG, "mlp_fwd_ln: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_fwd_ln: tensor exceeds 2 GB buffer range");
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_fwd_ln", {x, w1, b1, w2, b2, res, out, ln_gamma, ln_beta, ln_out, ln_mean, ln_rstd}, M, C,
+                               d, stream, a))
+        return e;
     if (res == out) return fail(CSU_E_ARG, "mlp_fwd_ln: out must not alias res");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
     const MlpLn ln{ln_gamma, ln_beta, ln_eps, (bf16*)ln_out, ln_mean, ln_rstd};
-    const hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 64: return fwd_launch<64>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st, &ln);
-        case 128: return fwd_launch<128>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st, &ln);
-        case 256: return fwd_launch<256>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st, &ln);
-        default: return fail(CSU_E_ARG, "mlp_fwd_ln: C must be 64, 128 or 256");
-    }
+    return dispatch_c("mlp_fwd_ln", C, CSU_E_ARG, [&](auto c) {
+        return fwd_launch<decltype(c)::value>(M, x, w1, b1, w2, b2, res, out, a.dp, a.rpi, a.st, &ln);
+    });
 }
 
 extern "C" int csu_mlp_fwd(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
@@ -2314,22 +2235,15 @@ extern "C" int csu_mlp_fwd(long M, int C, const void* x, const void* w1, const f
 
 extern "C" int csu_mlp_bwd_dp(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
                               void* dh, void* g, void* dx, const csu_mlp_dropout* d, void* stream) {
-    if (M < 1 || !x || !dy || !w1 || !b1 || !w2 || !dh || !g || !dx) return fail(CSU_E_ARG, "mlp_bwd: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_bwd: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
-    const hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 64: return bwd_launch<64>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_bwd", {x, dy, w1, b1, w2, dh, g, dx}, M, C, d, stream, a)) return e;
+    return dispatch_c("mlp_bwd", C, CSU_E_ARG, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
         // C = 128: the deep ring (4 chunks of 32 hidden in flight) measured 61.0 vs 75.2 us at 65536
-        // tokens (profiles/r06b_mlp8_probe.txt); C = 64 / 256: the per-panel kernels (equal or faster)
-        case 128: return bwd_deep_launch<128, 4>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-        case 256: return bwd_launch<256>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-        default: return fail(CSU_E_ARG, "mlp_bwd: C must be 64, 128 or 256");
-    }
+        // tokens (profiles/r06b_mlp8_probe.txt); C = 64 / 256: the persistent / per-panel kernels (equal or faster)
+        if constexpr (CC == 128) return bwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
+        else return bwd_launch<CC>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
+    });
 }
 
 extern "C" int csu_mlp_bwd(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
@@ -2353,21 +2267,17 @@ extern "C" int csu_mlp_bwd_wgrad(long M, int C, const void* x, const void* dy, c
                                  const void* w2, void* dx, const csu_mlp_dropout* d, float* slab1, float* slab2,
                                  csu_wslab_item* item1, csu_wslab_item* item2, float* dw1_db1, float* dw2_db2,
                                  void* stream) {
-    if (M < 1 || !x || !dy || !w1 || !b1 || !w2 || !dx || !slab1 || !slab2 || !item1 || !item2 || !dw1_db1 || !dw2_db2)
-        return fail(CSU_E_ARG, "mlp_bwd_wgrad: bad arguments");
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_bwd_wgrad", {x, dy, w1, b1, w2, dx, slab1, slab2, item1, item2, dw1_db1, dw2_db2}, M, C, d,
+                               stream, a))
+        return e;
     if (!csu_mlp_bwd_wgrad_supported(C)) return fail(CSU_E_ARG, "mlp_bwd_wgrad: C must be 64");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_bwd_wgrad: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
     const int grid = wgrad_grid(M);
-    const hipStream_t st = as_stream(stream);
-    if (d && e == 0)
-        mlp_bwd64_wgrad<true><<<dim3((unsigned)grid), 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
-                                                                       (const bf16*)w2, (bf16*)dx, slab1, slab2, md);
-    else
-        mlp_bwd64_wgrad<false><<<dim3((unsigned)grid), 2 * MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
-                                                                        (const bf16*)w2, (bf16*)dx, slab1, slab2, MlpDrop{});
+    with_flag(a.dp != nullptr, [&](auto df) {
+        mlp_bwd64<decltype(df)::value, true><<<dim3((unsigned)grid), 2 * MT, 0, a.st>>>(
+            M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2, nullptr, nullptr, (bf16*)dx, slab1, slab2,
+            a.dp ? a.md : MlpDrop{});
+    });
     *item1 = csu_wslab_item{slab1, dw1_db1, 4 * C, C, 32, 32, grid, 0};
     *item2 = csu_wslab_item{slab2, dw2_db2, C, 4 * C, 32, 32, grid, 0};
     return check_launch("mlp_bwd_wgrad");
@@ -2379,93 +2289,50 @@ extern "C" int csu_mlp_fp8_fwd_ln(long M, int C, const void* x, const void* w1q,
                                   const void* w2p, const float* sw2, const float* b2, const float* res, float* out,
                                   const csu_mlp_dropout* d, const float* ln_gamma, const float* ln_beta, float ln_eps,
                                   void* ln_out, float* ln_mean, float* ln_rstd, void* stream) {
-    if (M < 1 || !x || !w1q || !sw1 || !b1 || !w2p || !sw2 || !b2 || !res || !out || !ln_gamma || !ln_beta || !ln_out ||
-        !ln_mean || !ln_rstd)
-        return fail(CSU_E_ARG, "mlp_fp8_fwd_ln: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_fp8_fwd_ln: tensor exceeds 2 GB buffer range");
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_fp8_fwd_ln",
+                               {x, w1q, sw1, b1, w2p, sw2, b2, res, out, ln_gamma, ln_beta, ln_out, ln_mean, ln_rstd}, M, C, d,
+                               stream, a))
+        return e;
     if (res == out) return fail(CSU_E_ARG, "mlp_fp8_fwd_ln: out must not alias res");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
     const MlpLn ln{ln_gamma, ln_beta, ln_eps, (bf16*)ln_out, ln_mean, ln_rstd};
-    const hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 64: return fp8_fwd_launch<64>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, dp, rpi, st, &ln);
-        case 128: return fp8_fwd_launch<128>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, dp, rpi, st, &ln);
-        case 256: return fp8_fwd_launch<256>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, dp, rpi, st, &ln);
-        default: return fail(CSU_E_UNSUPPORTED, "mlp_fp8_fwd_ln: C must be 64, 128 or 256");
-    }
+    return dispatch_c("mlp_fp8_fwd_ln", C, CSU_E_UNSUPPORTED, [&](auto c) {
+        return fp8_fwd_launch<decltype(c)::value>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, a.dp, a.rpi, a.st, &ln);
+    });
 }
 
 extern "C" int csu_mlp_fp8_fwd(long M, int C, const void* x, const void* w1q, const float* sw1, const float* b1,
                                const void* w2p, const float* sw2, const float* b2, const float* res, float* out,
                                const csu_mlp_dropout* d, void* stream) {
-    if (M < 1 || !x || !w1q || !sw1 || !b1 || !w2p || !sw2 || !b2 || !res || !out)
-        return fail(CSU_E_ARG, "mlp_fp8_fwd: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_fp8_fwd: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
-    const hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 64: return fp8_fwd_launch<64>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, dp, rpi, st);
-        case 128: return fp8_fwd_launch<128>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, dp, rpi, st);
-        case 256: return fp8_fwd_launch<256>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, dp, rpi, st);
-        default: return fail(CSU_E_UNSUPPORTED, "mlp_fp8_fwd: C must be 64, 128 or 256");
-    }
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_fp8_fwd", {x, w1q, sw1, b1, w2p, sw2, b2, res, out}, M, C, d, stream, a)) return e;
+    return dispatch_c("mlp_fp8_fwd", C, CSU_E_UNSUPPORTED, [&](auto c) {
+        return fp8_fwd_launch<decltype(c)::value>(M, x, w1q, sw1, b1, w2p, sw2, b2, res, out, a.dp, a.rpi, a.st);
+    });
 }
 
 extern "C" int csu_mlp_fp8_bwd(long M, int C, const void* x, const void* dy, const void* w1q, const float* sw1,
                                const float* b1, const void* w2t, const float* sw2, const void* w1tp, void* dh, void* g,
                                void* dx, const csu_mlp_dropout* d, void* stream) {
-    if (M < 1 || !x || !dy || !w1q || !sw1 || !b1 || !w2t || !sw2 || !w1tp || !dh || !g || !dx)
-        return fail(CSU_E_ARG, "mlp_fp8_bwd: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_fp8_bwd: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
-    const hipStream_t st = as_stream(stream);
-    switch (C) {
-        case 64: return fp8_bwd_launch<64>(M, x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx, dp, rpi, st);
-        case 128: return fp8_bwd_launch<128>(M, x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx, dp, rpi, st);
-        case 256: return fp8_bwd_launch<256>(M, x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx, dp, rpi, st);
-        default: return fail(CSU_E_UNSUPPORTED, "mlp_fp8_bwd: C must be 64, 128 or 256");
-    }
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_fp8_bwd", {x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx}, M, C, d, stream, a)) return e;
+    return dispatch_c("mlp_fp8_bwd", C, CSU_E_UNSUPPORTED, [&](auto c) {
+        return fp8_bwd_launch<decltype(c)::value>(M, x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx, a.dp, a.rpi, a.st);
+    });
 }
 
-// explicit forward variant (tests, tools/mlp8_probe.py): cfg 0 = the per-panel kernel, 1 = the deep ring
+// explicit forward variant (tests, tools/mlp8_probe.py): cfg 0 = the per-panel kernel, 1 = the deep ring, 2 = deeper rings
 extern "C" int csu_mlp_fwd_ex(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                               const float* res, float* out, const csu_mlp_dropout* d, int cfg, void* stream) {
     if (cfg == 0) return csu_mlp_fwd_dp(M, C, x, w1, b1, w2, b2, res, out, d, stream);
     if (cfg != 1 && cfg != 2) return fail(CSU_E_ARG, "mlp_fwd_ex: cfg 0, 1 or 2");
-    if (M < 1 || !x || !w1 || !b1 || !w2 || !b2 || !res || !out) return fail(CSU_E_ARG, "mlp_fwd: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_fwd: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
-    const hipStream_t st = as_stream(stream);
-    if (cfg == 2) {   // deeper rings
-        switch (C) {
-            case 64: return fwd_deep_launch<64, 8>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-            case 128: return fwd_deep_launch<128, 6>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-            case 256: return fwd_deep_launch<256, 3>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-            default: return fail(CSU_E_ARG, "mlp_fwd: C must be 64, 128 or 256");
-        }
-    }
-    switch (C) {
-        case 64: return fwd_deep_launch<64, 6>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-        case 128: return fwd_deep_launch<128, 4>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-        case 256: return fwd_deep_launch<256, 4>(M, x, w1, b1, w2, b2, res, out, dp, rpi, st);
-        default: return fail(CSU_E_ARG, "mlp_fwd: C must be 64, 128 or 256");
-    }
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_fwd", {x, w1, b1, w2, b2, res, out}, M, C, d, stream, a)) return e;
+    return dispatch_c("mlp_fwd", C, CSU_E_ARG, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
+        return cfg == 2 ? fwd_deep_launch<CC, kDeepRs<CC, true>>(M, x, w1, b1, w2, b2, res, out, a.dp, a.rpi, a.st)
+                        : fwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, w1, b1, w2, b2, res, out, a.dp, a.rpi, a.st);
+    });
 }
 
 // explicit backward variant: cfg 0 = the per-panel / persistent kernels, 1 / 2 = the deep ring (csu_mlp_bwd_dp:
@@ -2473,34 +2340,12 @@ extern "C" int csu_mlp_fwd_ex(long M, int C, const void* x, const void* w1, cons
 extern "C" int csu_mlp_bwd_ex(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
                               void* dh, void* g, void* dx, const csu_mlp_dropout* d, int cfg, void* stream) {
     if (cfg != 0 && cfg != 1 && cfg != 2) return fail(CSU_E_ARG, "mlp_bwd_ex: cfg 0, 1 or 2");
-    if (M < 1 || !x || !dy || !w1 || !b1 || !w2 || !dh || !g || !dx) return fail(CSU_E_ARG, "mlp_bwd: bad arguments");
-    if (M * 4L * C * 2 > 0x7fffffffL) return fail(CSU_E_ARG, "mlp_bwd: tensor exceeds 2 GB buffer range");
-    MlpDrop md{};
-    const int e = mlp_drop_of(d, md);
-    if (e < 0) return e;
-    const MlpDrop* dp = d && e == 0 ? &md : nullptr;
-    const long rpi = d ? (long)d->rows_per_sample : 0;
-    const hipStream_t st = as_stream(stream);
-    if (cfg == 0) {   // the per-panel / persistent kernels
-        switch (C) {
-            case 64: return bwd_launch<64>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-            case 128: return bwd_launch<128>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-            case 256: return bwd_launch<256>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-            default: return fail(CSU_E_ARG, "mlp_bwd: C must be 64, 128 or 256");
-        }
-    }
-    if (cfg == 2) {
-        switch (C) {
-            case 64: return bwd_deep_launch<64, 8>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-            case 128: return bwd_deep_launch<128, 6>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-            case 256: return bwd_deep_launch<256, 3>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-            default: return fail(CSU_E_ARG, "mlp_bwd: C must be 64, 128 or 256");
-        }
-    }
-    switch (C) {
-        case 64: return bwd_deep_launch<64, 6>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-        case 128: return bwd_deep_launch<128, 4>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-        case 256: return bwd_deep_launch<256, 4>(M, x, dy, w1, b1, w2, dh, g, dx, dp, rpi, st);
-        default: return fail(CSU_E_ARG, "mlp_bwd: C must be 64, 128 or 256");
-    }
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_bwd", {x, dy, w1, b1, w2, dh, g, dx}, M, C, d, stream, a)) return e;
+    return dispatch_c("mlp_bwd", C, CSU_E_ARG, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
+        if (cfg == 0) return bwd_launch<CC>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
+        return cfg == 2 ? bwd_deep_launch<CC, kDeepRs<CC, true>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st)
+                        : bwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
+    });
 }

@@ -1753,6 +1753,48 @@ def _mlp_bwd_wgrad(M, C, x2, dyb, w1c, b1f, w2c, dx, dd, dts, params):
     return r1 + r2
 
 
+def _mlp_ln_side(ln, M, C, dev):
+    """Side outputs of a fused Mlp forward that also computes the next block's norm1 ``ln`` = (weight, bias,
+    eps): fp32 gamma, beta, eps, h1 (the bf16 LN output), mean, rstd, and the _LN_STASH tuple."""
+    gam, bet, eps = ln
+    h1 = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
+    mean = torch.empty(M, dtype=torch.float32, device=dev)
+    rstd = torch.empty(M, dtype=torch.float32, device=dev)
+    return (gam.detach().float().contiguous(), bet.detach().float().contiguous(), float(eps), h1, mean, rstd,
+            (gam, bet, float(eps), h1, mean, rstd))
+
+
+def _mlp_fused_bwd(ctx, dy, x2, w1c, b1f, w2c, launch=None):
+    """Gradients of (res, x, w1, b1, w2, b2) for _MlpFusedFn / _MlpFp8Fn: one csu_mlp_bwd_wgrad launch where
+    _mlp_bwd_wgrad takes it, else csu_mlp_bwd_dp (or ``launch(dyb, dh, g, dx, dd)``, the fp8 kernel, in
+    its place) and the two weight gradients."""
+    rdt, xshape, w1dt, b1dt, w2dt, b2dt = ctx.meta
+    M, C = x2.shape
+    drop = ctx.drop
+    if drop is None:
+        dyb = _bf16_of(dy).view(-1, C)
+    else:
+        dyb = drop.out_grad(dy.reshape(-1, C).contiguous(), torch.bfloat16)
+    dyb = dyb.contiguous()
+    dx = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
+    dd = ctypes.byref(_mlp_desc(drop, ctx.rpi))
+    fused = None if launch else _mlp_bwd_wgrad(M, C, x2, dyb, w1c, b1f, w2c, dx, dd, (w1dt, b1dt, w2dt, b2dt), ctx.params)
+    if fused is not None:
+        dw1, db1, dw2, db2 = fused
+    else:
+        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
+        g = torch.empty_like(dh)
+        if launch is not None:
+            launch(dyb, dh, g, dx, dd)
+        else:
+            _launch("mlp_bwd", lambda: lib().csu_mlp_bwd_dp(M, C, ptr(x2), ptr(dyb), ptr(w1c), ptr(b1f), ptr(w2c), ptr(dh),
+                                                            ptr(g), ptr(dx), dd, stream_ptr(x2.device)),
+                    24 * M * C * C, M * C * (2 + 2 + 2) + M * 4 * C * (2 + 2) + 16 * C * C)
+        dw2, db2 = wgrad_maybe_side(dyb, g, w2dt, b2dt, params=ctx.params[2:])
+        dw1, db1 = wgrad_maybe_side(dh, x2, w1dt, b1dt, params=ctx.params[:2])
+    return dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt)
+
+
 class _MlpFusedFn(torch.autograd.Function):
     """res + fc2(gelu(fc1(x))) (Mlp cswin:180-196 + residual cswin:368) in ONE csu_mlp_fwd launch
     (the 4C hidden layer never reaches HBM).  Backward: one csu_mlp_bwd launch recomputes h and
@@ -1773,16 +1815,12 @@ class _MlpFusedFn(torch.autograd.Function):
         dd = ctypes.byref(_mlp_desc(drop, rpi))
         if ln is not None:
             # + the next block's norm1 on the output (csu_mlp_fwd_ln); handed to its layer_norm_fork
-            gam, bet, eps = ln
-            gf, bf_ = gam.detach().float().contiguous(), bet.detach().float().contiguous()
-            h1 = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
-            mean = torch.empty(M, dtype=torch.float32, device=x2.device)
-            rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
+            gf, bf_, eps, h1, mean, rstd, stash = _mlp_ln_side(ln, M, C, x2.device)
             _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_ln(M, C, ptr(x2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
-                                                            ptr(y), dd, ptr(gf), ptr(bf_), float(eps), ptr(h1), ptr(mean),
+                                                            ptr(y), dd, ptr(gf), ptr(bf_), eps, ptr(h1), ptr(mean),
                                                             ptr(rstd), stream_ptr(x2.device)),
                     16 * M * C * C + 8 * M * C, M * C * (2 + 4 + 4 + 2) + 16 * C * C + 8 * M)
-            _LN_STASH[0] = (gam, bet, float(eps), h1, mean, rstd)
+            _LN_STASH[0] = stash
         else:
             _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_dp(M, C, ptr(x2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
                                                             ptr(y), dd, stream_ptr(x2.device)),
@@ -1797,29 +1835,8 @@ class _MlpFusedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        rdt, xshape, w1dt, b1dt, w2dt, b2dt = ctx.meta
         x2, w1c, b1f, w2c = ctx.saved_tensors
-        M, C = x2.shape
-        drop = ctx.drop
-        if drop is None:
-            dyb = _bf16_of(dy).view(-1, C)
-        else:
-            dyb = drop.out_grad(dy.reshape(-1, C).contiguous(), torch.bfloat16)
-        dx = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
-        dd = ctypes.byref(_mlp_desc(drop, ctx.rpi))
-        fused = _mlp_bwd_wgrad(M, C, x2, dyb, w1c, b1f, w2c, dx, dd, (w1dt, b1dt, w2dt, b2dt), ctx.params)
-        if fused is not None:
-            dw1, db1, dw2, db2 = fused
-            return (dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None,
-                    None, None)
-        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
-        g = torch.empty_like(dh)
-        _launch("mlp_bwd", lambda: lib().csu_mlp_bwd_dp(M, C, ptr(x2), ptr(dyb), ptr(w1c), ptr(b1f), ptr(w2c), ptr(dh),
-                                                        ptr(g), ptr(dx), dd, stream_ptr(x2.device)),
-                24 * M * C * C, M * C * (2 + 2 + 2) + M * 4 * C * (2 + 2) + 16 * C * C)
-        dw2, db2 = wgrad_maybe_side(dyb, g, w2dt, b2dt, params=ctx.params[2:])
-        dw1, db1 = wgrad_maybe_side(dh, x2, w1dt, b1dt, params=ctx.params[:2])
-        return dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None, None, None
+        return _mlp_fused_bwd(ctx, dy, x2, w1c, b1f, w2c) + (None,) * 4
 
 
 # the fused Mlp's LayerNorm of its output for the next block (csu_mlp_fwd_ln): (gamma, beta, eps, ln_out,
@@ -1885,16 +1902,12 @@ class _MlpFp8Fn(torch.autograd.Function):
         dd = ctypes.byref(_mlp_desc(drop, rpi))
         if ln is not None:
             # + the next block's norm1 on the output (csu_mlp_fp8_fwd_ln), as _MlpFusedFn
-            gam, bet, eps = ln
-            gf, bf_ = gam.detach().float().contiguous(), bet.detach().float().contiguous()
-            h1 = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
-            mean = torch.empty(M, dtype=torch.float32, device=x2.device)
-            rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
+            gf, bf_, eps, h1, mean, rstd, stash = _mlp_ln_side(ln, M, C, x2.device)
             _launch("mlp_fwd", lambda: lib().csu_mlp_fp8_fwd_ln(M, C, ptr(x2), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2p), ptr(sw2),
-                                                                ptr(b2f), ptr(res2), ptr(y), dd, ptr(gf), ptr(bf_), float(eps),
+                                                                ptr(b2f), ptr(res2), ptr(y), dd, ptr(gf), ptr(bf_), eps,
                                                                 ptr(h1), ptr(mean), ptr(rstd), stream_ptr(x2.device)),
                     16 * M * C * C + 8 * M * C, M * C * (2 + 4 + 4 + 2) + 8 * C * C + 8 * M, prec="fp8")
-            _LN_STASH[0] = (gam, bet, float(eps), h1, mean, rstd)
+            _LN_STASH[0] = stash
         else:
             _launch("mlp_fwd", lambda: lib().csu_mlp_fp8_fwd(M, C, ptr(x2), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2p), ptr(sw2),
                                                              ptr(b2f), ptr(res2), ptr(y), dd, stream_ptr(x2.device)),
@@ -1910,40 +1923,18 @@ class _MlpFp8Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        rdt, xshape, w1dt, b1dt, w2dt, b2dt = ctx.meta
         x2, b1f = ctx.saved_tensors
-        w1q, sw1, w2p, sw2, w2t, w1tp = ctx.ops8
         M, C = x2.shape
-        drop = ctx.drop
-        if drop is None:
-            dyb = _bf16_of(dy).view(-1, C)
-        else:
-            dyb = drop.out_grad(dy.reshape(-1, C).contiguous(), torch.bfloat16)
-        dyb = dyb.contiguous()
-        dx = torch.empty(M, C, dtype=torch.bfloat16, device=x2.device)
-        dd = ctypes.byref(_mlp_desc(drop, ctx.rpi))
-        if C not in FP8_MLP_BWD_C:
-            fused = _mlp_bwd_wgrad(M, C, x2, dyb, ctx.wc[0], b1f, ctx.wc[1], dx, dd, (w1dt, b1dt, w2dt, b2dt), ctx.params)
-            if fused is not None:
-                dw1, db1, dw2, db2 = fused
-                return (dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None,
-                        None, None, None)
-        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=x2.device)
-        g = torch.empty_like(dh)
+        fp8 = None
         if C in FP8_MLP_BWD_C:
-            _launch("mlp_bwd", lambda: lib().csu_mlp_fp8_bwd(M, C, ptr(x2), ptr(dyb), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2t),
-                                                             ptr(sw2), ptr(w1tp), ptr(dh), ptr(g), ptr(dx), dd,
-                                                             stream_ptr(x2.device)),
-                    24 * M * C * C, M * C * (2 + 2 + 2) + M * 4 * C * (2 + 2) + 12 * C * C, prec="fp8")
-        else:
-            w1c, w2c = ctx.wc
-            _launch("mlp_bwd", lambda: lib().csu_mlp_bwd_dp(M, C, ptr(x2), ptr(dyb), ptr(w1c), ptr(b1f), ptr(w2c), ptr(dh),
-                                                            ptr(g), ptr(dx), dd, stream_ptr(x2.device)),
-                    24 * M * C * C, M * C * (2 + 2 + 2) + M * 4 * C * (2 + 2) + 16 * C * C)
-        dw2, db2 = wgrad_maybe_side(dyb, g, w2dt, b2dt, params=ctx.params[2:])
-        dw1, db1 = wgrad_maybe_side(dh, x2, w1dt, b1dt, params=ctx.params[:2])
-        return (dy.to(rdt), dx.view(xshape), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None, None,
-                None, None)
+            w1q, sw1, w2p, sw2, w2t, w1tp = ctx.ops8
+
+            def fp8(dyb, dh, g, dx, dd):
+                _launch("mlp_bwd", lambda: lib().csu_mlp_fp8_bwd(M, C, ptr(x2), ptr(dyb), ptr(w1q), ptr(sw1), ptr(b1f),
+                                                                 ptr(w2t), ptr(sw2), ptr(w1tp), ptr(dh), ptr(g), ptr(dx), dd,
+                                                                 stream_ptr(x2.device)),
+                        24 * M * C * C, M * C * (2 + 2 + 2) + M * 4 * C * (2 + 2) + 12 * C * C, prec="fp8")
+        return _mlp_fused_bwd(ctx, dy, x2, ctx.wc[0], b1f, ctx.wc[1], fp8) + (None,) * 5
 
 
 def mlp_fp8(res, x, fc1: torch.nn.Linear, fc2: torch.nn.Linear, drop: Optional[MlpDrop] = None, ln=None):
