@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "csu.h"
 
@@ -237,5 +238,12 @@ __device__ __forceinline__ void gelu_pair_fast(float x, float& g, float& dg) {
 }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+template <bool V> using bconst = std::integral_constant<bool, V>;
+template <int V> using iconst = std::integral_constant<int, V>;
+// a launcher's runtime flag (dropout, LN) as a template argument: f(bconst<v>{})
+template <class F> void with_flag(bool v, F&& f) {
+    if (v) f(bconst<true>{}); else f(bconst<false>{});
+}
 
 }  // namespace csu

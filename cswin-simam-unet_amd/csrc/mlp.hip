@@ -241,13 +241,6 @@ __device__ __forceinline__ void bias16(const float* b1s, int base, int h, float*
     }
 }
 
-template <bool V> using bconst = std::integral_constant<bool, V>;
-template <int V> using iconst = std::integral_constant<int, V>;
-// a launcher's runtime flag (dropout, LN) as a template argument: f(bconst<v>{})
-template <class F> void with_flag(bool v, F&& f) {
-    if (v) f(bconst<true>{}); else f(bconst<false>{});
-}
-
 // Forward.  Rings: W1 chunks in 2 stages, W2 chunks in 2 stages.  Step j (after one barrier):
 // DMA W1(j+2), W2(j+1); GEMM1(j+1) on the MFMA pipe while GELU(j) runs on the VALU; GEMM2(j).
 // DROP: hidden / output dropout and DropPath (MlpDrop)
@@ -1261,14 +1254,14 @@ int fwd_launch(long M, const void* x, const void* w1, const float* b1, const voi
     const MlpLn l = ln ? *ln : MlpLn{};
     with_flag(ln != nullptr, [&](auto lnf) {
         constexpr bool LN = decltype(lnf)::value;
-        if constexpr (C == 256)
-            if (!d) {   // two waves per SIMD (dropout launches keep the 4-wave kernel)
-                mlp_fwd8_kernel<C, LN, kFwd8Hc><<<grid, 2 * MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, rpi, l);
-                return;
-            }
-        with_flag(d != nullptr, [&](auto df) {
-            mlp_fwd_kernel<C, decltype(df)::value, LN><<<grid, MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, dd, rpi, l);
-        });
+        if constexpr (C == 256) {   // two waves per SIMD; only dropout launches keep the 4-wave kernel
+            if (!d) mlp_fwd8_kernel<C, LN, kFwd8Hc><<<grid, 2 * MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, rpi, l);
+            else mlp_fwd_kernel<C, true, LN><<<grid, MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, dd, rpi, l);
+        } else {
+            with_flag(d != nullptr, [&](auto df) {
+                mlp_fwd_kernel<C, decltype(df)::value, LN><<<grid, MT, 0, st>>>(M, X, W1, b1, W2, b2, res, out, dd, rpi, l);
+            });
+        }
     });
     return check_launch(ln ? "mlp_fwd_ln" : "mlp_fwd");
 }
@@ -1279,20 +1272,20 @@ int bwd_launch(long M, const void* x, const void* dy, const void* w1, const floa
     const dim3 grid((unsigned)((M + BM - 1) / BM));
     const auto X = (const bf16*)x, dY = (const bf16*)dy, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
     const auto dH = (bf16*)dh, G = (bf16*)g, dX = (bf16*)dx;
-    if constexpr (C == 256)
-        if (!d) {   // two waves per SIMD (dropout launches keep the 4-wave kernel)
-            mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi);
-            return check_launch("mlp_bwd");
-        }
     const MlpDrop dd = d ? *d : MlpDrop{};
-    with_flag(d != nullptr, [&](auto df) {
-        constexpr bool D = decltype(df)::value;
-        if constexpr (C == 64)   // persistent, weights resident
-            mlp_bwd64<D, false><<<dim3((unsigned)persist_grid(M)), 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, nullptr,
-                                                                                    nullptr, dd);
-        else
-            mlp_bwd_kernel<C, D><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
-    });
+    if constexpr (C == 256) {   // two waves per SIMD; only dropout launches keep the 4-wave kernel
+        if (!d) mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi);
+        else mlp_bwd_kernel<C, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
+    } else {
+        with_flag(d != nullptr, [&](auto df) {
+            constexpr bool D = decltype(df)::value;
+            if constexpr (C == 64)   // persistent, weights resident
+                mlp_bwd64<D, false><<<dim3((unsigned)persist_grid(M)), 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX,
+                                                                                        nullptr, nullptr, dd);
+            else
+                mlp_bwd_kernel<C, D><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
+        });
+    }
     return check_launch("mlp_bwd");
 }
 

@@ -6,9 +6,36 @@
 // window token is gathered straight from the (B, L, 3C) qkv buffer and the result is written
 // straight to its channels of the (B, L, C) output.
 //
-// Work decomposition: one 256-thread workgroup = one (branch, image, window, head, 128-row
-// block); each of its 4 waves owns 32 rows.  The other operand streams through LDS in chunks of
-// KC = 128 rows.  All products are 32x32 MFMA tiles:
+// Dispatch map (N = tokens per window, DROP = attention dropout on; the launch layer is at the end):
+//   forward
+//     bf16, N <= 1024   stripe_fwd_w<WM, DROP, NW>, whole window in LDS, WM = 256 / 512 / 1024 >= N
+//     fp32, or N > 1024 stripe_fwd<T, DROP>, streamed (v1), one workgroup per 128-row block
+//   backward
+//     bf16, N <= 512    stripe_bwd_fused_w<WM, DROP, NW>, one pass, one workgroup per window-head:
+//                       <128, 4> for N <= 128, <256, 4> for N <= 256, else <512, 8>; also writes the
+//                       LePE weight-gradient partials (one block per image and window)
+//     bf16, N <= 1024   stripe_bwd_dq_w<1024, DROP, NW> + stripe_bwd_dkdv_w<1024, DROP, NW>
+//     fp32, or N > 1024 stripe_bwd_dq<T, DROP> + stripe_bwd_dkdv<T, DROP>, streamed (v1)
+//   LePE weight gradient (two passes, deterministic)
+//     pass 1            by the one-pass backward where that runs; else lepe_wgrad_tiles<T> if 4, 2 or
+//                       1 image rows with their halo fit 64 KiB of LDS, else lepe_wgrad_partial<T>
+//     pass 2            lepe_reduce_batch: right after pass 1 with the launch as its one item, or
+//                       deferred (csu_stripe_lepe_reduce_batch), many launches' partials at once
+//   The split kernels (stripe_fwd_w, stripe_bwd_dq_w / _dkdv_w) run wsplit() workgroups per
+//   window-head: enough for about 1024 workgroups per launch, each with at least 128 rows.  An even
+//   split runs as NW = 8 (two partners merged into one 8-wave workgroup), an odd one as NW = 4.
+#include <cstdlib>
+
+#include "common.hpp"
+#include "rng.hpp"
+
+namespace csu {
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// v1, streamed.  Work decomposition: one 256-thread workgroup = one (branch, image, window, head,
+// 128-row block); each of its 4 waves owns 32 rows.  The other operand streams through LDS in
+// chunks of KC = 128 rows.  All products are 32x32 MFMA tiles:
 //   bf16 storage: v_mfma_f32_32x32x16_bf16 (fp32 accumulate);
 //   fp32 storage: v_mfma_f32_32x32x2_f32  (exact f32 fma chain -- the fp32 parity path).
 // "Swapped" orientation: S^T = K Q^T puts the query on the lane and 16 keys in registers, so
@@ -17,16 +44,7 @@
 //
 // Backward = two kernels (query-owner: dQ and delta; key-owner: dK, dV including the LePE
 // input gradient) plus a deterministic two-pass reduction for the LePE weight/bias gradient.
-#include <cstdlib>
-
-#include "common.hpp"
-#include "rng.hpp"
-
-#include <type_traits>
-
-namespace csu {
-namespace {
-
+// ---------------------------------------------------------------------------------------------
 constexpr int HD = 32;     // head dim (fixed by the model: SURVEY §0.5)
 constexpr int KC = 128;    // rows of the streamed operand per LDS chunk
 constexpr int QR = 128;    // rows owned by one workgroup (4 waves x 32)
@@ -208,9 +226,11 @@ __device__ __forceinline__ void lepe4(const Win& w, int reso, const T* img, int 
 }
 
 constexpr int LW_IT = (HD * 10 + NT - 1) / NT;
-// the two halves of stage_lepe_weights for the whole-window kernels: issue the loads, and (after the
-// window staging loads have been issued) write LDS -- the LDS write waits for its loads, and vmcnt
-// counts in issue order, so writing right after the loads would drain everything issued before
+// LePE weights and bias of head h in two halves: issue the loads, and (in the whole-window kernels,
+// after the window staging loads have been issued) write LDS -- the LDS write waits for its loads, and
+// vmcnt counts in issue order, so writing right after the loads would drain everything issued before.
+// Branch-free (raw buffer loads, masked lanes out of range): a predicated load here made hipcc wait
+// vmcnt(0) before the window staging loads that follow
 __device__ __forceinline__ void lepe_weights_load(const csu_stripe_branch& g, int h, float* v) {
     const __amdgpu_buffer_rsrc_t rw = buf_rsrc(g.lepe_w + h * HD * 9, HD * 9 * 4), rb = buf_rsrc(g.lepe_b + h * HD, HD * 4);
 #pragma unroll
@@ -234,22 +254,12 @@ __device__ __forceinline__ void lepe_weights_store(const float* v, float* wts) {
     }
 }
 
+// streamed (v1) kernels: load and store at once, LDS layout as in memory ([channel][tap], then the bias)
 __device__ __forceinline__ void stage_lepe_weights(const csu_stripe_branch& g, int h, float* wts) {
-    constexpr int IT = (HD * 10 + NT - 1) / NT;
-    float v[IT];
-    // branch-free (raw buffer loads, masked lanes out of range): a predicated load here made hipcc
-    // wait vmcnt(0) before the window staging loads that follow
-    const __amdgpu_buffer_rsrc_t rw = buf_rsrc(g.lepe_w + h * HD * 9, HD * 9 * 4), rb = buf_rsrc(g.lepe_b + h * HD, HD * 4);
+    float v[LW_IT];
+    lepe_weights_load(g, h, v);
 #pragma unroll
-    for (int k = 0; k < IT; ++k) {
-        const int i = threadIdx.x + k * NT;
-        const float a = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, i < HD * 9 ? (unsigned)i * 4u : kOOB, 0, 0));
-        const float b = __uint_as_float(
-            __builtin_amdgcn_raw_buffer_load_b32(rb, (i >= HD * 9 && i < HD * 10) ? (unsigned)(i - HD * 9) * 4u : kOOB, 0, 0));
-        v[k] = i < HD * 9 ? a : b;
-    }
-#pragma unroll
-    for (int k = 0; k < IT; ++k)
+    for (int k = 0; k < LW_IT; ++k)
         if (threadIdx.x + k * NT < HD * 10) wts[threadIdx.x + k * NT] = v[k];
 }
 
@@ -807,11 +817,9 @@ int lepe_rows_blk(const csu_stripe_args& a, int ty) {
     return (int)((rows + ty - 1) / ty * ty);
 }
 
-// one wave per (branch, value): lanes stride over the block partials (contiguous), then a fixed
-// xor-shuffle tree -- deterministic
-// 16 lanes per value (the block partials are 32..128 per value at the model's sizes: a wave per value
-// left lanes idle and launched 4x the waves); shared with lepe_reduce_batch, so the deferred batched
-// reduction is bitwise equal to this one
+// pass 2, one value of lepe_reduce_batch: 16 lanes per value stride over its block partials
+// (contiguous), then a fixed xor-shuffle tree -- deterministic (the block partials are 32..128 per
+// value at the model's sizes: a wave per value left lanes idle and launched 4x the waves)
 // (nblk % 4 == 0: 16-B loads of 4 consecutive partials, four in flight per lane -- the fused
 // backward leaves B * windows = 256..2048 partials per value, ~60 MB per step at 512x512 B16)
 __device__ __forceinline__ float lepe_value_sum(const float* __restrict__ src, int nblk, int sub) {
@@ -835,19 +843,6 @@ __device__ __forceinline__ float lepe_value_sum(const float* __restrict__ src, i
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     return s;
-}
-
-__global__ __launch_bounds__(256) void lepe_wgrad_reduce(csu_stripe_args a, int nblk, const float* __restrict__ part) {
-    const int Cb = a.heads * HD, vt = a.nbranch * Cb * 10;
-    const int v = blockIdx.x * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;
-    const float s = lepe_value_sum(part + (size_t)(v < vt ? v : vt - 1) * nblk, nblk, sub);
-    if (sub == 0 && v < vt) {
-        const int br = v / (Cb * 10), i = v % (Cb * 10);
-        const csu_stripe_branch& g = branch(a, br);
-        const int c = i / 10, k = i % 10;
-        if (k < 9) g.lepe_dw[c * 9 + k] = s;
-        else g.lepe_db[c] = s;
-    }
 }
 
 int wgrad_blocks(const csu_stripe_args& a) {
@@ -1826,22 +1821,30 @@ __global__ __launch_bounds__(64 * NW, WM <= 256 ? 2 : 1) void stripe_bwd_fused_w
     ATT_STAMP(1, 4);
 }
 
+// =============================================================================================
+// Launch layer (host).  Which kernel serves which launch: the dispatch map at the top of the file.
+// =============================================================================================
+// window tokens N and windows per image of a launch (validate: every branch has N tokens per window)
+struct Geo { int N, nwin; };
+Geo geo_of(const csu_stripe_args& a) {
+    const csu_stripe_branch& g = a.br[0];
+    return {g.H_sp * g.W_sp, (a.reso / g.H_sp) * (a.reso / g.W_sp)};
+}
+// grid of k workgroups per (image, window, head); the streamed kernels take one per 128-row block
+dim3 wgrid(const csu_stripe_args& a, int k) { return dim3(a.B * geo_of(a).nwin * a.heads * k, a.nbranch); }
+dim3 grid_of(const csu_stripe_args& a) { return wgrid(a, (geo_of(a).N + QR - 1) / QR); }
+
 // the one-pass backward handles the launch (bf16, window <= 512 tokens: WM = 512 holds the four
 // window images in 128 KiB of LDS, one workgroup per CU)
-bool use_fused_bwd(const csu_stripe_args& a, int dtype) {
-    return dtype == CSU_BF16 && a.br[0].H_sp * a.br[0].W_sp <= 512;
-}
-int fused_nblk(const csu_stripe_args& a) {
-    return a.B * (a.reso / a.br[0].H_sp) * (a.reso / a.br[0].W_sp);
-}
+bool use_fused_bwd(const csu_stripe_args& a, int dtype) { return dtype == CSU_BF16 && geo_of(a).N <= 512; }
+int fused_nblk(const csu_stripe_args& a) { return a.B * geo_of(a).nwin; }
 
 template <int WM, int NW = 4>
 void bwd_fused(const csu_stripe_args& a, const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, bf16* dqkv,
                float* part, hipStream_t st) {
-    const int nwin = (a.reso / a.br[0].H_sp) * (a.reso / a.br[0].W_sp);
-    const dim3 g(a.B * nwin * a.heads, a.nbranch);
-    if (a.drop_p > 0.f) stripe_bwd_fused_w<WM, true, NW><<<g, 64 * NW, 0, st>>>(a, qkv, out, dout, lse, dqkv, part);
-    else stripe_bwd_fused_w<WM, false, NW><<<g, 64 * NW, 0, st>>>(a, qkv, out, dout, lse, dqkv, part);
+    with_flag(a.drop_p > 0.f, [&](auto df) {
+        stripe_bwd_fused_w<WM, decltype(df)::value, NW><<<wgrid(a, 1), 64 * NW, 0, st>>>(a, qkv, out, dout, lse, dqkv, part);
+    });
 }
 
 // split factor of the whole-window kernels: workgroups per window-head, so that a launch has
@@ -1851,21 +1854,18 @@ void bwd_fused(const csu_stripe_args& a, const bf16* qkv, const bf16* out, const
 #define ATTN_SPLIT_WGS 1024
 #endif
 int wsplit(const csu_stripe_args& a) {
-    const int N = a.br[0].H_sp * a.br[0].W_sp;
-    const int nwin = (a.reso / a.br[0].H_sp) * (a.reso / a.br[0].W_sp);
-    const long wgs = (long)a.B * nwin * a.heads * a.nbranch;
-    const int maxsp = (((N + 31) & ~31) + 127) / 128;
+    const Geo w = geo_of(a);
+    const long wgs = (long)a.B * w.nwin * a.heads * a.nbranch;
+    const int maxsp = (((w.N + 31) & ~31) + 127) / 128;
     const long want = (ATTN_SPLIT_WGS + wgs - 1) / wgs;
     return (int)(want < maxsp ? want : maxsp);
 }
 
-bool use_window_path(const csu_stripe_args& a, int dtype) {
-    return dtype == CSU_BF16 && a.br[0].H_sp * a.br[0].W_sp <= WMAX;
-}
+bool use_window_path(const csu_stripe_args& a, int dtype) { return dtype == CSU_BF16 && geo_of(a).N <= WMAX; }
 
-// LDS image rows of a launch: the window rounded up to 256 / 512 / 1024 tokens
+// LDS image rows of a forward launch: the window rounded up to 256 / 512 / 1024 tokens
 int wm_of(const csu_stripe_args& a) {
-    const int N = a.br[0].H_sp * a.br[0].W_sp;
+    const int N = geo_of(a).N;
     return N <= 256 ? 256 : N <= 512 ? 512 : 1024;
 }
 
@@ -1878,42 +1878,36 @@ int wm_of(const csu_stripe_args& a) {
 #define ATTN_BWD_WAVES 8
 #endif
 template <int WM>
-void fwd_w(const csu_stripe_args& a, int sp, dim3 g, const bf16* qkv, bf16* out, float* lse, hipStream_t st) {
-    if (ATTN_FWD_WAVES == 8 && sp % 2 == 0) {
-        g.x /= 2;
-        if (a.drop_p > 0.f) stripe_fwd_w<WM, true, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, out, lse);
-        else stripe_fwd_w<WM, false, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, out, lse);
-        return;
-    }
-    if (a.drop_p > 0.f) stripe_fwd_w<WM, true><<<g, NT, 0, st>>>(a, sp, qkv, out, lse);
-    else stripe_fwd_w<WM, false><<<g, NT, 0, st>>>(a, sp, qkv, out, lse);
+void fwd_w(const csu_stripe_args& a, const bf16* qkv, bf16* out, float* lse, hipStream_t st) {
+    const int sp = wsplit(a);
+    with_flag(a.drop_p > 0.f, [&](auto df) {
+        constexpr bool D = decltype(df)::value;
+        if (ATTN_FWD_WAVES == 8 && sp % 2 == 0)
+            stripe_fwd_w<WM, D, 8><<<wgrid(a, sp / 2), 512, 0, st>>>(a, sp / 2, qkv, out, lse);
+        else
+            stripe_fwd_w<WM, D><<<wgrid(a, sp), NT, 0, st>>>(a, sp, qkv, out, lse);
+    });
 }
 
-template <int WM>
-void bwd_w(const csu_stripe_args& a, int sp, dim3 g, const bf16* qkv, const bf16* out, const bf16* dout,
-           const float* lse, float* delta, bf16* dqkv, hipStream_t st) {
-    // windows of >= 512 tokens (their K / V or Q / dO images bound residency): split partners merged
-    // into 8-wave workgroups, as the forward (ATTN_FWD_WAVES)
-    if constexpr (WM >= 512) {
+// The split whole-window backward.  Only windows of 513..1024 tokens get here (windows of at most 512
+// tokens take stripe_bwd_fused_w: use_fused_bwd), so the LDS images always have WMAX rows.  Their
+// K / V or Q / dO images bound residency: split partners merged into 8-wave workgroups, as the
+// forward (ATTN_FWD_WAVES)
+void bwd_w(const csu_stripe_args& a, const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, float* delta,
+           bf16* dqkv, hipStream_t st) {
+    const int sp = wsplit(a);
+    with_flag(a.drop_p > 0.f, [&](auto df) {
+        constexpr bool D = decltype(df)::value;
         if (ATTN_BWD_WAVES == 8 && sp % 2 == 0) {
-            g.x /= 2;
-            if (a.drop_p > 0.f) {
-                stripe_bwd_dq_w<WM, true, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, out, dout, lse, delta, dqkv);
-                stripe_bwd_dkdv_w<WM, true, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, dout, lse, delta, dqkv);
-            } else {
-                stripe_bwd_dq_w<WM, false, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, out, dout, lse, delta, dqkv);
-                stripe_bwd_dkdv_w<WM, false, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, dout, lse, delta, dqkv);
-            }
-            return;
+            const dim3 g = wgrid(a, sp / 2);
+            stripe_bwd_dq_w<WMAX, D, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, out, dout, lse, delta, dqkv);
+            stripe_bwd_dkdv_w<WMAX, D, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, dout, lse, delta, dqkv);
+        } else {
+            const dim3 g = wgrid(a, sp);
+            stripe_bwd_dq_w<WMAX, D><<<g, NT, 0, st>>>(a, sp, qkv, out, dout, lse, delta, dqkv);
+            stripe_bwd_dkdv_w<WMAX, D><<<g, NT, 0, st>>>(a, sp, qkv, dout, lse, delta, dqkv);
         }
-    }
-    if (a.drop_p > 0.f) {
-        stripe_bwd_dq_w<WM, true><<<g, NT, 0, st>>>(a, sp, qkv, out, dout, lse, delta, dqkv);
-        stripe_bwd_dkdv_w<WM, true><<<g, NT, 0, st>>>(a, sp, qkv, dout, lse, delta, dqkv);
-    } else {
-        stripe_bwd_dq_w<WM, false><<<g, NT, 0, st>>>(a, sp, qkv, out, dout, lse, delta, dqkv);
-        stripe_bwd_dkdv_w<WM, false><<<g, NT, 0, st>>>(a, sp, qkv, dout, lse, delta, dqkv);
-    }
+    });
 }
 
 int validate(const csu_stripe_args* a, int dtype) {
@@ -1941,21 +1935,30 @@ int validate(const csu_stripe_args* a, int dtype) {
 }
 
 template <typename T>
-void bwd_generic(const csu_stripe_args& a, dim3 grid, const T* qkv, const T* out, const T* dout, const float* lse,
-                 float* delta, T* dqkv, hipStream_t st) {
-    if (a.drop_p > 0.f) {
-        stripe_bwd_dq<T, true><<<grid, NT, 0, st>>>(a, qkv, out, dout, lse, delta, dqkv);
-        stripe_bwd_dkdv<T, true><<<grid, NT, 0, st>>>(a, qkv, dout, lse, delta, dqkv);
-    } else {
-        stripe_bwd_dq<T, false><<<grid, NT, 0, st>>>(a, qkv, out, dout, lse, delta, dqkv);
-        stripe_bwd_dkdv<T, false><<<grid, NT, 0, st>>>(a, qkv, dout, lse, delta, dqkv);
-    }
+void fwd_generic(const csu_stripe_args& a, const void* qkv, void* out, float* lse, hipStream_t st) {
+    with_flag(a.drop_p > 0.f, [&](auto df) {
+        stripe_fwd<T, decltype(df)::value><<<grid_of(a), NT, 0, st>>>(a, (const T*)qkv, (T*)out, lse);
+    });
 }
 
-dim3 grid_of(const csu_stripe_args& a) {
-    const int N = a.br[0].H_sp * a.br[0].W_sp;
-    const int nwin = (a.reso / a.br[0].H_sp) * (a.reso / a.br[0].W_sp);
-    return dim3(a.B * nwin * a.heads * ((N + QR - 1) / QR), a.nbranch);
+template <typename T>
+void bwd_generic(const csu_stripe_args& a, const void* qkv, const void* out, const void* dout, const float* lse,
+                 float* delta, void* dqkv, hipStream_t st) {
+    const dim3 grid = grid_of(a);
+    with_flag(a.drop_p > 0.f, [&](auto df) {
+        constexpr bool D = decltype(df)::value;
+        stripe_bwd_dq<T, D><<<grid, NT, 0, st>>>(a, (const T*)qkv, (const T*)out, (const T*)dout, lse, delta, (T*)dqkv);
+        stripe_bwd_dkdv<T, D><<<grid, NT, 0, st>>>(a, (const T*)qkv, (const T*)dout, lse, delta, (T*)dqkv);
+    });
+}
+
+// LePE weight-gradient layout (lepe_wgrad_partial, stripe_bwd_fused_w): the channel quads of a branch
+// are a power of two dividing NT
+int check_lepe_layout(const csu_stripe_args& a, const char* who) {
+    const int nq = a.heads * HD / 4;
+    if (NT % nq || (nq & (nq - 1)))
+        return fail(CSU_E_UNSUPPORTED, std::string(who) + ": heads per branch must be a power of two <= 32");
+    return 0;
 }
 
 }  // namespace
@@ -1967,24 +1970,18 @@ extern "C" int csu_stripe_attn_fwd(const csu_stripe_args* a, int dtype, const vo
                                    float* lse, void* stream) {
     if (int e = validate(a, dtype)) return e;
     if (!qkv || !out || !lse) return fail(CSU_E_ARG, "stripe_attn_fwd: null buffer");
+    const hipStream_t st = as_stream(stream);
     if (use_window_path(*a, dtype)) {
-        const int sp = wsplit(*a);
-        const int nwin = (a->reso / a->br[0].H_sp) * (a->reso / a->br[0].W_sp);
-        const dim3 g(a->B * nwin * a->heads * sp, a->nbranch);
-        const hipStream_t st = as_stream(stream);
         switch (wm_of(*a)) {
-            case 256: fwd_w<256>(*a, sp, g, (const bf16*)qkv, (bf16*)out, lse, st); break;
-            case 512: fwd_w<512>(*a, sp, g, (const bf16*)qkv, (bf16*)out, lse, st); break;
-            default: fwd_w<1024>(*a, sp, g, (const bf16*)qkv, (bf16*)out, lse, st); break;
+            case 256: fwd_w<256>(*a, (const bf16*)qkv, (bf16*)out, lse, st); break;
+            case 512: fwd_w<512>(*a, (const bf16*)qkv, (bf16*)out, lse, st); break;
+            default: fwd_w<1024>(*a, (const bf16*)qkv, (bf16*)out, lse, st); break;
         }
-        return check_launch("stripe_attn_fwd");
+    } else if (dtype == CSU_BF16) {
+        fwd_generic<bf16>(*a, qkv, out, lse, st);
+    } else {
+        fwd_generic<float>(*a, qkv, out, lse, st);
     }
-    const dim3 grid = grid_of(*a);
-    const bool drop = a->drop_p > 0.f;
-    if (dtype == CSU_BF16 && drop) stripe_fwd<bf16, true><<<grid, NT, 0, as_stream(stream)>>>(*a, (const bf16*)qkv, (bf16*)out, lse);
-    else if (dtype == CSU_BF16) stripe_fwd<bf16, false><<<grid, NT, 0, as_stream(stream)>>>(*a, (const bf16*)qkv, (bf16*)out, lse);
-    else if (drop) stripe_fwd<float, true><<<grid, NT, 0, as_stream(stream)>>>(*a, (const float*)qkv, (float*)out, lse);
-    else stripe_fwd<float, false><<<grid, NT, 0, as_stream(stream)>>>(*a, (const float*)qkv, (float*)out, lse);
     return check_launch("stripe_attn_fwd");
 }
 
@@ -2007,8 +2004,8 @@ struct LpBatch {
     int count;
 };
 
-// lanes as lepe_wgrad_reduce; each item's value range starts on a multiple of 16 (v0), so the
-// workgroup's item is found by a uniform scan on blockIdx (scalar loads of the item table)
+// 16 lanes per value (lepe_value_sum); each item's value range starts on a multiple of 16 (v0), so
+// the workgroup's item is found by a uniform scan on blockIdx (scalar loads of the item table)
 __global__ __launch_bounds__(256) void lepe_reduce_batch(LpBatch t) {
     const int w0 = blockIdx.x * 16;
     int i = 0;
@@ -2025,8 +2022,42 @@ __global__ __launch_bounds__(256) void lepe_reduce_batch(LpBatch t) {
     }
 }
 
-void lepe_wgrad_launch(const csu_stripe_args& a, int dtype, const void* qkv, const void* dout, float* part, hipStream_t st,
-                       bool reduce = true) {
+// pass 2 of every LePE weight gradient, LPB_MAX items per launch.  Launches only: the callers check the items
+void lepe_reduce_launch(const csu_lepe_reduce_item* items, int count, hipStream_t st) {
+    for (int i0 = 0; i0 < count; i0 += LPB_MAX) {
+        LpBatch t;
+        t.count = count - i0 < LPB_MAX ? count - i0 : LPB_MAX;
+        t.v0[0] = 0;
+        for (int k = 0; k < t.count; ++k) {
+            const csu_lepe_reduce_item& it = items[i0 + k];
+            t.part[k] = it.part;
+            t.dw[k][0] = it.dw[0]; t.dw[k][1] = it.nbranch > 1 ? it.dw[1] : it.dw[0];
+            t.db[k][0] = it.db[0]; t.db[k][1] = it.nbranch > 1 ? it.db[1] : it.db[0];
+            t.nblk[k] = it.nblk;
+            t.cb[k] = it.channels;
+            t.nbranch[k] = it.nbranch;
+            t.v0[k + 1] = t.v0[k] + (it.nbranch * it.channels * 10 + 15) / 16 * 16;
+        }
+        lepe_reduce_batch<<<(unsigned)((t.v0[t.count] + 15) / 16), 256, 0, st>>>(t);
+    }
+}
+
+// the inline reduction: the nblk block partials of a launch as one item, into the gradients of its args
+void lepe_reduce_inline(const csu_stripe_args& a, int nblk, const float* part, hipStream_t st) {
+    csu_lepe_reduce_item it = {};
+    it.part = part;
+    it.nblk = nblk;
+    it.channels = a.heads * HD;
+    it.nbranch = a.nbranch;
+    for (int b = 0; b < a.nbranch; ++b) {
+        it.dw[b] = a.br[b].lepe_dw;
+        it.db[b] = a.br[b].lepe_db;
+    }
+    lepe_reduce_launch(&it, 1, st);
+}
+
+// pass 1 (block partials) for the launches whose attention backward does not form them itself
+void lepe_wgrad_launch(const csu_stripe_args& a, int dtype, const void* qkv, const void* dout, float* part, hipStream_t st) {
     const int ty = lepe_tile_rows(a, dtype);
     const int nblk = lepe_nblk(a, dtype);
     if (ty) {
@@ -2041,9 +2072,6 @@ void lepe_wgrad_launch(const csu_stripe_args& a, int dtype, const void* qkv, con
     } else {
         lepe_wgrad_partial<float><<<dim3(nblk, a.nbranch), NT, 0, st>>>(a, (const float*)qkv, (const float*)dout, part);
     }
-    if (!reduce) return;
-    const dim3 rgrid((a.nbranch * a.heads * HD * 10 + 15) / 16);
-    lepe_wgrad_reduce<<<rgrid, 256, 0, st>>>(a, nblk, part);
 }
 
 extern "C" size_t csu_stripe_attn_bwd_workspace(const csu_stripe_args* a) {
@@ -2055,16 +2083,6 @@ extern "C" size_t csu_stripe_attn_bwd_workspace(const csu_stripe_args* a) {
     return (size_t)a->nbranch * n * a->heads * HD * 10 * sizeof(float);
 }
 
-extern "C" int csu_stripe_attn_bwd_ex(const csu_stripe_args* a, int dtype, const void* qkv, const void* out,
-                                      const void* dout, const float* lse, float* delta, void* dqkv,
-                                      void* workspace, size_t workspace_bytes, int lepe_deferred, void* stream);
-
-extern "C" int csu_stripe_attn_bwd(const csu_stripe_args* a, int dtype, const void* qkv, const void* out,
-                                   const void* dout, const float* lse, float* delta, void* dqkv,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-    return csu_stripe_attn_bwd_ex(a, dtype, qkv, out, dout, lse, delta, dqkv, workspace, workspace_bytes, 0, stream);
-}
-
 // partial blocks csu_stripe_attn_bwd_ex(lepe_deferred = 1) leaves in its workspace
 extern "C" int csu_stripe_lepe_nblk(const csu_stripe_args* a, int dtype) {
     if (!a) return 0;
@@ -2073,33 +2091,14 @@ extern "C" int csu_stripe_lepe_nblk(const csu_stripe_args* a, int dtype) {
 
 extern "C" int csu_stripe_lepe_reduce_batch(const csu_lepe_reduce_item* items, int count, void* stream) {
     if (count < 0 || (count && !items)) return fail(CSU_E_ARG, "stripe_lepe_reduce_batch: bad args");
-    LpBatch t;
-    t.count = 0;
-    t.v0[0] = 0;
-    auto flush = [&]() -> int {
-        if (!t.count) return 0;
-        lepe_reduce_batch<<<(unsigned)((t.v0[t.count] + 15) / 16), 256, 0, as_stream(stream)>>>(t);
-        t.count = 0;
-        return check_launch("stripe_lepe_reduce_batch");
-    };
     for (int i = 0; i < count; ++i) {
         const csu_lepe_reduce_item& it = items[i];
         if (!it.part || it.nblk < 1 || it.channels < 1 || it.nbranch < 1 || it.nbranch > 2) return fail(CSU_E_ARG, "stripe_lepe_reduce_batch: bad item");
         for (int b = 0; b < it.nbranch; ++b)
             if (!it.dw[b] || !it.db[b]) return fail(CSU_E_ARG, "stripe_lepe_reduce_batch: null gradient");
-        if (t.count == LPB_MAX)
-            if (int e = flush()) return e;
-        const int k = t.count;
-        t.part[k] = it.part;
-        t.dw[k][0] = it.dw[0]; t.dw[k][1] = it.nbranch > 1 ? it.dw[1] : it.dw[0];
-        t.db[k][0] = it.db[0]; t.db[k][1] = it.nbranch > 1 ? it.db[1] : it.db[0];
-        t.nblk[k] = it.nblk;
-        t.cb[k] = it.channels;
-        t.nbranch[k] = it.nbranch;
-        t.v0[k + 1] = t.v0[k] + (it.nbranch * it.channels * 10 + 15) / 16 * 16;
-        t.count = k + 1;
     }
-    return flush();
+    lepe_reduce_launch(items, count, as_stream(stream));
+    return check_launch("stripe_lepe_reduce_batch");
 }
 
 extern "C" int csu_stripe_attn_bwd_ex(const csu_stripe_args* a, int dtype, const void* qkv, const void* out,
@@ -2114,45 +2113,32 @@ extern "C" int csu_stripe_attn_bwd_ex(const csu_stripe_args* a, int dtype, const
     if (nnull && nnull != 2 * a->nbranch) return fail(CSU_E_ARG, "stripe_attn_bwd: null LePE grads");
     if (do_lepe && (workspace_bytes < csu_stripe_attn_bwd_workspace(a) || !workspace))
         return fail(CSU_E_WORKSPACE, "stripe_attn_bwd: workspace too small");
-    {
-        const int nq = a->heads * HD / 4;   // LePE weight-gradient layout: channel quads per branch
-        if (NT % nq || (nq & (nq - 1)))
-            return fail(CSU_E_UNSUPPORTED, "stripe_attn_bwd: heads per branch must be a power of two <= 32");
-    }
-    hipStream_t st = as_stream(stream);
-    const dim3 grid = grid_of(*a);
+    if (int e = check_lepe_layout(*a, "stripe_attn_bwd")) return e;
+    const hipStream_t st = as_stream(stream);
     float* part = (float*)workspace;
     if (use_fused_bwd(*a, dtype)) {
         // one pass: dQ, dK, dV and (do_lepe) the LePE weight-gradient partials, reduced below or deferred
         const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *go = (const bf16*)dout;
         float* pp = do_lepe ? part : nullptr;
-        const int N = a->br[0].H_sp * a->br[0].W_sp;
+        const int N = geo_of(*a).N;
         if (N <= 128) bwd_fused<128>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
         else if (N <= 256) bwd_fused<256>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
         else bwd_fused<512, 8>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
-        if (do_lepe && !lepe_deferred) {
-            const dim3 rgrid((a->nbranch * a->heads * HD * 10 + 15) / 16);
-            lepe_wgrad_reduce<<<rgrid, 256, 0, st>>>(*a, fused_nblk(*a), part);
-        }
-        return check_launch("stripe_attn_bwd");
-    }
-    if (use_window_path(*a, dtype)) {
-        const int sp = wsplit(*a);
-        const int nwin = (a->reso / a->br[0].H_sp) * (a->reso / a->br[0].W_sp);
-        const dim3 g(a->B * nwin * a->heads * sp, a->nbranch);
-        const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *go = (const bf16*)dout;
-        switch (wm_of(*a)) {
-            case 256: bwd_w<256>(*a, sp, g, q, o, go, lse, delta, (bf16*)dqkv, st); break;
-            case 512: bwd_w<512>(*a, sp, g, q, o, go, lse, delta, (bf16*)dqkv, st); break;
-            default: bwd_w<1024>(*a, sp, g, q, o, go, lse, delta, (bf16*)dqkv, st); break;
-        }
-    } else if (dtype == CSU_BF16) {
-        bwd_generic<bf16>(*a, grid, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, st);
     } else {
-        bwd_generic<float>(*a, grid, (const float*)qkv, (const float*)out, (const float*)dout, lse, delta, (float*)dqkv, st);
+        if (use_window_path(*a, dtype))
+            bwd_w(*a, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, st);
+        else if (dtype == CSU_BF16) bwd_generic<bf16>(*a, qkv, out, dout, lse, delta, dqkv, st);
+        else bwd_generic<float>(*a, qkv, out, dout, lse, delta, dqkv, st);
+        if (do_lepe) lepe_wgrad_launch(*a, dtype, qkv, dout, part, st);
     }
-    if (do_lepe) lepe_wgrad_launch(*a, dtype, qkv, dout, part, st, !lepe_deferred);
+    if (do_lepe && !lepe_deferred) lepe_reduce_inline(*a, csu_stripe_lepe_nblk(a, dtype), part, st);
     return check_launch("stripe_attn_bwd");
+}
+
+extern "C" int csu_stripe_attn_bwd(const csu_stripe_args* a, int dtype, const void* qkv, const void* out,
+                                   const void* dout, const float* lse, float* delta, void* dqkv,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    return csu_stripe_attn_bwd_ex(a, dtype, qkv, out, dout, lse, delta, dqkv, workspace, workspace_bytes, 0, stream);
 }
 
 extern "C" int csu_stripe_lepe_wgrad(const csu_stripe_args* a, int dtype, const void* qkv, const void* dout,
@@ -2163,9 +2149,9 @@ extern "C" int csu_stripe_lepe_wgrad(const csu_stripe_args* a, int dtype, const 
         if (!a->br[i].lepe_dw || !a->br[i].lepe_db) return fail(CSU_E_ARG, "stripe_lepe_wgrad: null LePE grads");
     if (workspace_bytes < csu_stripe_attn_bwd_workspace(a) || !workspace)
         return fail(CSU_E_WORKSPACE, "stripe_lepe_wgrad: workspace too small");
-    const int nq = a->heads * HD / 4;
-    if (NT % nq || (nq & (nq - 1))) return fail(CSU_E_UNSUPPORTED, "stripe_lepe_wgrad: heads per branch must be a power of two <= 32");
+    if (int e = check_lepe_layout(*a, "stripe_lepe_wgrad")) return e;
     lepe_wgrad_launch(*a, dtype, qkv, dout, (float*)workspace, as_stream(stream));
+    lepe_reduce_inline(*a, lepe_nblk(*a, dtype), (const float*)workspace, as_stream(stream));
     return check_launch("stripe_lepe_wgrad");
 }
 

@@ -43,6 +43,7 @@ ATTN_CASES = [
     (64, 0, 8, 64, 2, 1), (20, -1, 20, 32, 1, 2), (24, -1, 24, 64, 2, 1), (32, -1, 32, 128, 4, 1),
     # the 512x512 headline's stage-1 (reso 128, width-1 stripes of 128 tokens, cswin:232-237) and stage-2 windows
     (128, 0, 1, 32, 1, 1), (128, 1, 1, 32, 1, 1), (64, 0, 2, 64, 2, 1),
+    (42, -1, 42, 64, 2, 1),   # 1764 tokens (ragged): above the LDS-resident windows, the streamed kernels in bf16 too
 ]
 
 
