@@ -1,0 +1,587 @@
+// Fused multi-class segmentation loss  w_ce * CE + w_tversky * mean_r mean_{c in C}(1 - TI_rc)  on
+// K-class logits z (fp32 or bf16, upcast in registers) and integer labels t (uint8 or int64), with
+// the hard (argmax) per-class sums of the training loop's Dice / IoU from the same pass.  The
+// reference trains one class only (num_classes=1, cswin:924) and has no counterpart.
+//   p = softmax_k(z) (max-subtracted, fp32);  pixels with t == ignore_index contribute to no sum
+//   CE    = sum_pix w[t] (logsumexp(z) - z_t) / sum_pix w[t]                      (whole batch)
+//   TP_rc = sum p_c [t = c],  P_rc = sum p_c,  T_rc = sum [t = c]                 (row r: batch or image)
+//   D = (1 - a - b) TP + a P + b T + smooth,  TI = (TP + smooth) / D
+//   hard: pred = argmax_k z (lowest index wins a tie);  I_c = sum [pred = c][t = c],  Pr_c = sum [pred = c]
+//
+// Work split (seg_loss.hip's): an image's HW pixels are cut into cpi chunks of clen pixels
+// (clen % 4 == 0); one workgroup reduces one (image, chunk) item at a time, items beyond the grid
+// are walked grid-stride.  A row of the Tversky term is one image (rows = B) or all of them (rows = 1).
+//   forward 1  ce_partial: 2 + 5 K sums per item (CE numerator, sum w, and per class TP, P, T, I, Pr)
+//              -> workspace[item][2 + 5 K].  A thread keeps p_c and p_c [t = c] sums per class in a
+//              fixed pixel order; the three counts are wave ballots (integers: exact in any order);
+//              then a fixed shuffle + LDS tree.  No atomics.
+//   forward 2  ce_finish (one workgroup, fp64): wave w sums the items of the (row, class) pairs w,
+//              w + 4, ...; writes loss, stats (3, K) fp64 [I; Pr; T], per (row, class) the backward
+//              coefficients A = (D - (TP + smooth)(1 - a - b)) / D^2, C = a (TP + smooth) / D^2 (zero for
+//              an excluded background), and 1 / sum w (0 when every pixel is ignored: CE and its
+//              gradient are then 0, not NaN).
+//   backward   ce_backward: recomputes the softmax and writes, in the logits' dtype and strides,
+//              dz_k = g [w_ce w[t] (p_k - [k = t]) / sum w - (w_tv / (R |C|)) p_k (G_k - sum_c G_c p_c)],
+//              G_c = A_rc [t = c] - C_rc.
+// Logits are addressed by element strides (s_b, s_k, s_pix).  Three access modes:
+//   class-last vector  s_k = 1, every pixel's K logits start on a vector boundary and the bucket
+//              KB >= K is readable per pixel (K == KB, or a padded pitch: the token GEMM's n8):
+//              one thread per pixel, 16-B loads.
+//   NCHW       s_pix = 1: a thread owns V = 4 / 2 / 1 (KB <= 8 / 16 / 32) consecutive pixels of every
+//              class, V-wide loads on units that lie inside the chunk on a vector boundary; the
+//              first / last unit of a chunk that starts off a boundary are read per element.
+//   strided    anything else (dense class-last with K != KB): per-element loads.
+// No label ever indexes memory (class weight and z_t are selected by comparison), so a label
+// outside [0, K) cannot fault; it matches no class.  The summation order is a function of the
+// shape, the strides and the address mod 16 only.
+#include "common.hpp"
+
+namespace csu {
+namespace {
+
+constexpr int NT = 256;
+constexpr int CE_BLOCKS = 1024;
+constexpr int KMAX = 32;
+constexpr float kLog2eLo = 1.92596299e-8f;   // log2(e) - (float)log2(e)
+
+enum { MODE_CL = 0, MODE_NCHW = 1, MODE_GEN = 2 };
+
+struct CePlan {
+    long clen, items;
+    int cpi;
+};
+
+CePlan ce_plan(int B, long HW) {
+    CePlan s;
+    const long maxc = B < CE_BLOCKS ? CE_BLOCKS / B : 1;
+    long cpi = (HW + 4 * NT - 1) / (4 * NT);
+    cpi = cpi < 1 ? 1 : cpi > maxc ? maxc : cpi;
+    s.clen = ((HW + cpi - 1) / cpi + 3) & ~3L;
+    s.cpi = (int)((HW + s.clen - 1) / s.clen);
+    s.items = (long)B * s.cpi;
+    return s;
+}
+
+inline int ce_nsum(int K) { return 2 + 5 * K; }
+inline int ce_bucket(int K) { return K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : 32; }
+constexpr int ce_vec(int KB, int mode) { return mode != MODE_NCHW ? 1 : KB <= 8 ? 4 : KB == 16 ? 2 : 1; }
+
+struct CeArgs {
+    int B, K, cpi, lab64;
+    long HW, clen, items, s_b, s_k, s_pix, ignore;
+    const void* z;
+    const void* t;
+    const float* cw;
+};
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// exp(x), x <= 0: v_exp_f32 of the product x log2(e) with the product's rounding error and the
+// constant's put back (relative error ~1 ulp over the whole range instead of |x| 2^-24).  Below
+// -200 the result is 0 in fp32 anyway; the clamp keeps x = -inf (a bucket's unused classes) out of
+// the error term, where inf - inf would make a NaN
+__device__ __forceinline__ float exp_neg(float x) {
+    x = fmaxf(x, -200.f);
+    const float h = x * kLog2e;
+    const float l = fmaf(x, kLog2e, -h) + x * kLog2eLo;
+    const float r = __builtin_amdgcn_exp2f(h);
+    return fmaf(r, l * kLn2, r);
+}
+
+template <int V, typename T> __device__ __forceinline__ void loadv(const T* p, float* v) {
+    if constexpr (V == 1) {
+        v[0] = (float)p[0];
+    } else {
+        typedef T vec __attribute__((ext_vector_type(V)));
+        const vec x = *reinterpret_cast<const vec*>(p);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = (float)x[j];
+    }
+}
+template <int V, typename T> __device__ __forceinline__ void storev(T* p, const float* v) {
+    if constexpr (V == 1) {
+        p[0] = (T)v[0];
+    } else {
+        typedef T vec __attribute__((ext_vector_type(V)));
+        vec x;
+#pragma unroll
+        for (int j = 0; j < V; ++j) x[j] = (T)v[j];
+        *reinterpret_cast<vec*>(p) = x;
+    }
+}
+// widest access of a class-last pixel's KB elements: 16 B, or all of it when that is less
+template <typename T, int KB> constexpr int cl_vec() { return KB * (int)sizeof(T) >= 16 ? 16 / (int)sizeof(T) : KB; }
+
+// One unit = V pixels e0 .. e0 + V - 1 of image base zb; pixels outside [lo, hi) are dead.
+// z[j][k] = logit of pixel j, class k; 0 for a dead pixel, -inf for k >= K.
+template <typename T, int KB, int MODE, int V>
+__device__ __forceinline__ void load_unit(const CeArgs& a, const T* zb, long e0, long lo, long hi, bool full,
+                                          float (&z)[V][KB]) {
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+#pragma unroll
+        for (int k = 0; k < KB; ++k) z[j][k] = k < a.K ? 0.f : -INFINITY;
+    if constexpr (MODE == MODE_CL) {
+        if (e0 >= lo && e0 < hi) {
+            constexpr int W = cl_vec<T, KB>();
+            float v[KB];
+#pragma unroll
+            for (int k = 0; k < KB; k += W) loadv<W>(zb + e0 * a.s_pix + k, v + k);
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (k < a.K) z[0][k] = v[k];
+        }
+    } else if constexpr (MODE == MODE_NCHW) {
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            if (k < a.K) {
+                const T* q = zb + k * a.s_k + e0;
+                if (full) {
+                    float v[V];
+                    loadv<V>(q, v);
+#pragma unroll
+                    for (int j = 0; j < V; ++j) z[j][k] = v[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < V; ++j)
+                        if (e0 + j >= lo && e0 + j < hi) z[j][k] = (float)q[j];
+                }
+            }
+        }
+    } else {
+        if (e0 >= lo && e0 < hi) {
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (k < a.K) z[0][k] = (float)zb[e0 * a.s_pix + k * a.s_k];
+        }
+    }
+}
+
+// label of pixel e of image b as a class index, -1 when the pixel is dead, ignored or out of range
+__device__ __forceinline__ int load_label(const CeArgs& a, long b, long e, long lo, long hi, bool& live) {
+    live = false;
+    if (e < lo || e >= hi) return -1;
+    const long i = b * a.HW + e;
+    const long v = a.lab64 ? ((const long*)a.t)[i] : (long)((const unsigned char*)a.t)[i];
+    live = v != a.ignore;
+    return live && v >= 0 && v < a.K ? (int)v : -1;
+}
+
+// softmax of one pixel in place (z -> p), returns max and sum of exp; arg = first maximum
+template <int KB> __device__ __forceinline__ void softmax_px(float (&z)[KB], float& m, float& s, int& arg) {
+    m = z[0];
+    arg = 0;
+#pragma unroll
+    for (int k = 1; k < KB; ++k)
+        if (z[k] > m) {
+            m = z[k];
+            arg = k;
+        }
+    s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+        z[k] = exp_neg(z[k] - m);
+        s += z[k];
+    }
+    const float inv = 1.f / s;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) z[k] *= inv;
+}
+
+// the units of item `it`: image b, pixels [lo, hi), first unit at e_first (<= lo, on a V boundary of
+// the logits' address when the vector form applies), nu units
+template <typename T, int V>
+__device__ __forceinline__ void item_range(const CeArgs& a, long it, bool vec_ok, long& b, long& lo, long& hi,
+                                           long& e_first, long& nu) {
+    b = it / a.cpi;
+    lo = (it - b * a.cpi) * a.clen;
+    hi = min(lo + a.clen, a.HW);
+    long pre = 0;
+    if (V > 1 && vec_ok) pre = (long)((((uintptr_t)a.z / sizeof(T)) + (unsigned long)(b * a.s_b + lo)) % V);
+    e_first = lo - pre;
+    nu = (hi - e_first + V - 1) / V;
+}
+
+template <typename T, int KB, int MODE>
+__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __restrict__ partial) {
+    constexpr int V = ce_vec(KB, MODE);
+    constexpr bool LANE_CNT = KB >= 16;
+    constexpr int NC = LANE_CNT ? 1 : KB;
+    __shared__ float red[NT / 64][2 + 5 * KB];
+    const int K = a.K, ns = 2 + 5 * K;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float cw[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) cw[k] = (a.cw && k < K) ? a.cw[k] : 1.f;
+    for (long it = blockIdx.x; it < a.items; it += gridDim.x) {
+        long b, lo, hi, e_first, nu;
+        item_range<T, V>(a, it, vec_ok, b, lo, hi, e_first, nu);
+        const T* zb = (const T*)a.z + b * a.s_b;
+        float ce = 0.f, sw = 0.f, tp[KB], ps[KB];
+        // counts: wave-uniform ballot sums, one scalar per class (small buckets) or held by lane k for
+        // class k (KB >= 16: 3 registers instead of 3 KB)
+        int ct[NC], ci[NC], cp[NC];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) tp[k] = ps[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) ct[k] = ci[k] = cp[k] = 0;
+        auto count = [&](int (&c)[NC], int k, bool pred) {
+            const int n = __popcll(__ballot(pred));
+            if constexpr (LANE_CNT) c[0] += lane == k ? n : 0; else c[k] += n;
+        };
+        for (long ub = 0; ub < nu; ub += NT) {   // the same trip count in every lane: ballots see whole waves
+            const long u = ub + threadIdx.x;
+            const long e0 = e_first + u * V;
+            const bool full = vec_ok && e0 >= lo && e0 + V <= hi;
+            float z[V][KB];
+            load_unit<T, KB, MODE, V>(a, zb, e0, lo, hi, full, z);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                bool live;
+                const int t = load_label(a, b, e0 + j, lo, hi, live);
+                float zt = 0.f, wt = 0.f;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    zt = t == k ? z[j][k] : zt;
+                    wt = t == k ? cw[k] : wt;
+                }
+                float m, s;
+                int arg;
+                softmax_px<KB>(z[j], m, s, arg);
+                ce += live ? wt * ((logf(s) + m) - zt) : 0.f;
+                sw += wt;
+                const int pred = live ? arg : -1;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    const float pk = live ? z[j][k] : 0.f;
+                    ps[k] += pk;
+                    tp[k] += t == k ? pk : 0.f;
+                    count(ct, k, t == k);
+                    count(cp, k, pred == k);
+                    count(ci, k, pred == k && t == k);
+                }
+            }
+        }
+        ce = wave_sum(ce);
+        sw = wave_sum(sw);
+        if (lane == 0) {
+            red[wv][0] = ce;
+            red[wv][1] = sw;
+        }
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            const float wtp = wave_sum(tp[k]), wps = wave_sum(ps[k]);
+            if (lane == 0 && k < K) {
+                red[wv][2 + k] = wtp;
+                red[wv][2 + K + k] = wps;
+                if constexpr (!LANE_CNT) {
+                    red[wv][2 + 2 * K + k] = (float)ct[k];
+                    red[wv][2 + 3 * K + k] = (float)ci[k];
+                    red[wv][2 + 4 * K + k] = (float)cp[k];
+                }
+            }
+        }
+        if constexpr (LANE_CNT) {
+            if (lane < K) {
+                red[wv][2 + 2 * K + lane] = (float)ct[0];
+                red[wv][2 + 3 * K + lane] = (float)ci[0];
+                red[wv][2 + 4 * K + lane] = (float)cp[0];
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < ns; i += NT)
+            partial[it * ns + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+        __syncthreads();
+    }
+}
+
+// coef: rows x K x 2 floats (A, C), then 1 / sum w
+__global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows, const float* __restrict__ partial,
+                                                float w_ce, float w_tv, float alpha, float beta, float smooth, int bg,
+                                                float* __restrict__ loss, double* __restrict__ stats,
+                                                float* __restrict__ coef) {
+    __shared__ double red[3][NT / 64];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ns = 2 + 5 * K;
+    const long items = (long)B * cpi;
+    const long ipr = rows == 1 ? items : cpi;   // items per row
+    const double a = alpha, b = beta, g = 1.0 - a - b, sm = smooth;
+    double atv = 0.;
+    for (long pr = w; pr < (long)rows * K; pr += NT / 64) {
+        const long r = pr / K;
+        const int c = (int)(pr - r * K);
+        double TP = 0., P = 0., T = 0.;
+        for (long i = lane; i < ipr; i += 64) {
+            const float* q = partial + (r * ipr + i) * ns + 2 + c;
+            TP += (double)q[0];
+            P += (double)q[K];
+            T += (double)q[2 * K];
+        }
+        TP = wave_sum_d(TP);
+        P = wave_sum_d(P);
+        T = wave_sum_d(T);
+        const bool on = bg || c > 0;
+        const double num = TP + sm, D = g * TP + a * P + b * T + sm, inv = 1.0 / D;
+        if (lane == 0) {
+            coef[2 * pr] = on ? (float)((D - num * g) * inv * inv) : 0.f;
+            coef[2 * pr + 1] = on ? (float)(a * num * inv * inv) : 0.f;
+        }
+        if (on) atv += (a * (P - TP) + b * (T - TP)) * inv;   // 1 - TI without the cancellation of 1 - num / D
+    }
+    if (stats)
+        for (int c = w; c < K; c += NT / 64) {
+            double I = 0., Pr = 0., T = 0.;
+            for (long i = lane; i < items; i += 64) {
+                const float* q = partial + i * ns + 2 + 2 * K + c;
+                T += (double)q[0];
+                I += (double)q[K];
+                Pr += (double)q[2 * K];
+            }
+            I = wave_sum_d(I);
+            Pr = wave_sum_d(Pr);
+            T = wave_sum_d(T);
+            if (lane == 0) {
+                stats[c] = I;
+                stats[K + c] = Pr;
+                stats[2 * K + c] = T;
+            }
+        }
+    double ce = 0., sw = 0.;
+    for (long i = threadIdx.x; i < items; i += NT) {
+        ce += (double)partial[i * ns];
+        sw += (double)partial[i * ns + 1];
+    }
+    ce = wave_sum_d(ce);
+    sw = wave_sum_d(sw);
+    if (lane == 0) {
+        red[0][w] = atv;
+        red[1][w] = ce;
+        red[2][w] = sw;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tot[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+        const double isw = tot[2] > 0. ? 1.0 / tot[2] : 0.;
+        const int nc = bg ? K : K - 1;
+        loss[0] = (float)((double)w_ce * tot[1] * isw + (double)w_tv * tot[0] / ((double)rows * nc));
+        coef[2 * (long)rows * K] = (float)isw;
+    }
+}
+
+template <typename T, int KB, int MODE>
+__global__ __launch_bounds__(NT) void ce_backward(CeArgs a, int vec_ok, int rows, const float* __restrict__ dloss,
+                                                  const float* __restrict__ coef, float w_ce, float tv_scale,
+                                                  T* __restrict__ dz) {
+    constexpr int V = ce_vec(KB, MODE);
+    const int K = a.K;
+    const float g = dloss[0], g1 = g * w_ce * coef[2 * (long)rows * K], g2 = g * tv_scale;
+    float cw[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) cw[k] = (a.cw && k < K) ? a.cw[k] : 1.f;
+    for (long it = blockIdx.x; it < a.items; it += gridDim.x) {
+        long b, lo, hi, e_first, nu;
+        item_range<T, V>(a, it, vec_ok, b, lo, hi, e_first, nu);
+        const T* zb = (const T*)a.z + b * a.s_b;
+        T* db = dz + b * a.s_b;
+        const float* cf = coef + 2 * (rows == 1 ? 0 : b) * K;
+        float A[KB], C[KB];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            A[k] = k < K ? cf[2 * k] : 0.f;
+            C[k] = k < K ? cf[2 * k + 1] : 0.f;
+        }
+        for (long ub = 0; ub < nu; ub += NT) {
+            const long u = ub + threadIdx.x;
+            const long e0 = e_first + u * V;
+            const bool full = vec_ok && e0 >= lo && e0 + V <= hi;
+            float z[V][KB];
+            load_unit<T, KB, MODE, V>(a, zb, e0, lo, hi, full, z);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                bool live;
+                const int t = load_label(a, b, e0 + j, lo, hi, live);
+                float wt = 0.f;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) wt = t == k ? cw[k] : wt;
+                float m, s;
+                int arg;
+                softmax_px<KB>(z[j], m, s, arg);
+                float dot = 0.f;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) dot += ((t == k ? A[k] : 0.f) - C[k]) * z[j][k];
+                const float c1 = g1 * wt;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    const float pk = z[j][k], G = (t == k ? A[k] : 0.f) - C[k];
+                    const float d = c1 * (pk - (t == k ? 1.f : 0.f)) - g2 * pk * (G - dot);
+                    z[j][k] = live ? d : 0.f;
+                }
+            }
+            if constexpr (MODE == MODE_CL) {
+                if (e0 >= lo && e0 < hi) {
+                    constexpr int W = cl_vec<T, KB>();
+#pragma unroll
+                    for (int k = 0; k < KB; ++k)
+                        if (k >= K) z[0][k] = 0.f;
+#pragma unroll
+                    for (int k = 0; k < KB; k += W) storev<W>(db + e0 * a.s_pix + k, &z[0][k]);
+                }
+            } else if constexpr (MODE == MODE_NCHW) {
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    if (k < K) {
+                        T* q = db + k * a.s_k + e0;
+                        if (full) {
+                            float v[V];
+#pragma unroll
+                            for (int j = 0; j < V; ++j) v[j] = z[j][k];
+                            storev<V>(q, v);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < V; ++j)
+                                if (e0 + j >= lo && e0 + j < hi) q[j] = (T)z[j][k];
+                        }
+                    }
+                }
+            } else {
+                if (e0 >= lo && e0 < hi) {
+#pragma unroll
+                    for (int k = 0; k < KB; ++k)
+                        if (k < K) db[e0 * a.s_pix + k * a.s_k] = (T)z[0][k];
+                }
+            }
+        }
+    }
+}
+
+// the access mode of a logits tensor and whether its vector form applies; dz (bwd) shares the strides
+template <typename T> int ce_mode(int K, int KB, const void* z, const void* dz, long s_b, long s_k, long s_pix, int pad_ok,
+                                  int* vec_ok) {
+    *vec_ok = 0;
+    const uintptr_t za = (uintptr_t)z, da = dz ? (uintptr_t)dz : za;
+    if (s_k == 1 && s_pix >= KB && (K == KB || pad_ok)) {
+        const long W = KB * (long)sizeof(T) >= 16 ? 16 / (long)sizeof(T) : KB;
+        const uintptr_t wb = (uintptr_t)W * sizeof(T);
+        if (za % wb == 0 && da % wb == 0 && s_pix % W == 0 && s_b % W == 0) return MODE_CL;
+    }
+    if (s_pix == 1) {
+        const long V = ce_vec(KB, MODE_NCHW);
+        // every class plane and image starts at the same offset within a vector; dz at the logits' offset
+        *vec_ok = V > 1 && s_k % V == 0 && s_b % V == 0 && za % sizeof(T) == 0 &&
+                  (za / sizeof(T)) % V == (da / sizeof(T)) % V && da % sizeof(T) == 0;
+        return MODE_NCHW;
+    }
+    return MODE_GEN;
+}
+
+template <class F> void with_bucket(int KB, F&& f) {
+    switch (KB) {
+        case 4: f(iconst<4>{}); break;
+        case 8: f(iconst<8>{}); break;
+        case 16: f(iconst<16>{}); break;
+        default: f(iconst<32>{}); break;
+    }
+}
+template <class F> void with_mode(int mode, F&& f) {
+    switch (mode) {
+        case MODE_CL: f(iconst<MODE_CL>{}); break;
+        case MODE_NCHW: f(iconst<MODE_NCHW>{}); break;
+        default: f(iconst<MODE_GEN>{}); break;
+    }
+}
+
+int ce_args(const char* what, int B, int K, long HW, int rows, int dtype, long s_b, long s_k, long s_pix, int label_dtype,
+            float w_ce, float w_tv) {
+    const std::string w(what);
+    if (B < 1 || HW < 1) return fail(CSU_E_ARG, w + ": B and HW must be >= 1");
+    if (K < 2 || K > KMAX) return fail(CSU_E_ARG, w + ": 2 <= K <= 32 classes (more: the caller's torch composition)");
+    if (rows != 1 && rows != B) return fail(CSU_E_ARG, w + ": rows must be 1 or B");
+    if (dtype != CSU_F32 && dtype != CSU_BF16) return fail(CSU_E_ARG, w + ": logits dtype must be f32 or bf16");
+    if (label_dtype != 0 && label_dtype != 1) return fail(CSU_E_ARG, w + ": label_dtype must be 0 (uint8) or 1 (int64)");
+    if (s_k < 1 || s_pix < 1 || s_b < 0) return fail(CSU_E_ARG, w + ": strides must be positive");
+    if (!(w_ce >= 0.f) || !(w_tv >= 0.f)) return fail(CSU_E_ARG, w + ": w_ce and w_tversky must be >= 0");
+    if (w_ce == 0.f && w_tv == 0.f) return fail(CSU_E_ARG, w + ": w_ce and w_tversky are both zero");
+    return 0;
+}
+
+CeArgs ce_pack(int B, int K, long HW, const void* z, long s_b, long s_k, long s_pix, int label_dtype, const void* t,
+               long ignore, const float* cw) {
+    const CePlan s = ce_plan(B, HW);
+    CeArgs a;
+    a.B = B; a.K = K; a.cpi = s.cpi; a.lab64 = label_dtype;
+    a.HW = HW; a.clen = s.clen; a.items = s.items; a.s_b = s_b; a.s_k = s_k; a.s_pix = s_pix; a.ignore = ignore;
+    a.z = z; a.t = t; a.cw = cw;
+    return a;
+}
+
+}  // namespace
+}  // namespace csu
+
+using namespace csu;
+
+extern "C" size_t csu_seg_ce_workspace(int B, int K, long HW) {
+    if (B < 1 || HW < 1 || K < 2 || K > KMAX) return 0;
+    return (size_t)ce_plan(B, HW).items * ce_nsum(K) * sizeof(float);
+}
+
+extern "C" int csu_seg_ce_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                              int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                              float w_ce, float w_tversky, float alpha, float beta, float smooth, int include_background,
+                              float* loss, double* stats, float* coef, void* workspace, size_t ws_bytes, void* stream) {
+    if (int e = ce_args("seg_ce_fwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky)) return e;
+    if (!(alpha >= 0.f) || !(beta >= 0.f)) return fail(CSU_E_ARG, "seg_ce_fwd: alpha and beta must be >= 0");
+    if (!(smooth > 0.f)) return fail(CSU_E_ARG, "seg_ce_fwd: smooth must be > 0");
+    if (!z || !t || !loss || !coef) return fail(CSU_E_ARG, "seg_ce_fwd: null z, t, loss or coef");
+    if (!workspace || ws_bytes < csu_seg_ce_workspace(B, K, HW)) return fail(CSU_E_WORKSPACE, "seg_ce_fwd: workspace");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    const int KB = ce_bucket(K);
+    const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
+    hipStream_t st = as_stream(stream);
+    int vec_ok = 0;
+    const int mode = dtype == CSU_F32 ? ce_mode<float>(K, KB, z, nullptr, s_b, s_k, s_pix, pad_ok, &vec_ok)
+                                            : ce_mode<bf16>(K, KB, z, nullptr, s_b, s_k, s_pix, pad_ok, &vec_ok);
+    with_flag(dtype == CSU_F32, [&](auto f32) {
+        using T = std::conditional_t<decltype(f32)::value, float, bf16>;
+        with_bucket(KB, [&](auto kb) {
+            with_mode(mode, [&](auto md) {
+                ce_partial<T, decltype(kb)::value, decltype(md)::value><<<nb, NT, 0, st>>>(a, vec_ok, (float*)workspace);
+            });
+        });
+    });
+    if (int e = check_launch("seg_ce_fwd")) return e;
+    ce_finish<<<1, NT, 0, st>>>(B, K, a.cpi, rows, (const float*)workspace, w_ce, w_tversky, alpha, beta, smooth,
+                                include_background != 0, loss, stats, coef);
+    return check_launch("seg_ce_fwd");
+}
+
+extern "C" int csu_seg_ce_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                              int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                              const float* dloss, const float* coef, float w_ce, float w_tversky, int include_background,
+                              void* dz, void* stream) {
+    if (int e = ce_args("seg_ce_bwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky)) return e;
+    if (!z || !t || !dloss || !coef || !dz) return fail(CSU_E_ARG, "seg_ce_bwd: null z, t, dloss, coef or dz");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    const int KB = ce_bucket(K);
+    const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
+    hipStream_t st = as_stream(stream);
+    int vec_ok = 0;
+    const int mode = dtype == CSU_F32 ? ce_mode<float>(K, KB, z, dz, s_b, s_k, s_pix, pad_ok, &vec_ok)
+                                            : ce_mode<bf16>(K, KB, z, dz, s_b, s_k, s_pix, pad_ok, &vec_ok);
+    const float tv_scale = w_tversky / ((float)rows * (float)(include_background ? K : K - 1));
+    with_flag(dtype == CSU_F32, [&](auto f32) {
+        using T = std::conditional_t<decltype(f32)::value, float, bf16>;
+        with_bucket(KB, [&](auto kb) {
+            with_mode(mode, [&](auto md) {
+                ce_backward<T, decltype(kb)::value, decltype(md)::value>
+                    <<<nb, NT, 0, st>>>(a, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
+            });
+        });
+    });
+    return check_launch("seg_ce_bwd");
+}

@@ -11,7 +11,8 @@ from .simam import SimAM, simam
 from .unet import DoubleConv, Down, UNet, Up
 from .train import (bce_loss, dice_coefficient, evaluate_model, iou_score, make_optimizer, make_scheduler,
                     train_model, train_step)
-from .losses import SegLoss, bce_dice_loss, dice_loss, tversky_loss
+from .losses import (MultiClassSegLoss, SegLoss, bce_dice_loss, ce_dice_loss, ce_loss, dice_loss, multiclass_dice_loss,
+                     tversky_loss)
 from .optim import FusedAdam, FusedAdamW
 from . import rng
 from .rng import manual_seed
@@ -19,4 +20,5 @@ from .rng import manual_seed
 __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock", "CSWinTransformer", "DropPath", "LePEAttention", "Merge_Block", "Mlp",
            "img2windows", "windows2img", "SimAM", "simam", "bce_loss", "dice_coefficient", "evaluate_model",
            "iou_score", "make_optimizer", "make_scheduler", "train_model", "train_step", "FusedAdamW", "FusedAdam",
-           "rng", "manual_seed", "SegLoss", "dice_loss", "bce_dice_loss", "tversky_loss"]
+           "rng", "manual_seed", "SegLoss", "dice_loss", "bce_dice_loss", "tversky_loss",
+           "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss"]

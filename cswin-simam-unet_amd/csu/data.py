@@ -9,8 +9,12 @@ import numpy as np
 import torch
 
 
-def ellipse_sample(rng: np.random.Generator, size: int):
-    """One (image, mask) pair as numpy arrays (3,S,S) / (1,S,S)."""
+def ellipse_sample(rng: np.random.Generator, size: int, num_classes: int = 1):
+    """One (image, mask) pair as numpy arrays (3,S,S) / (1,S,S).  num_classes > 1: every ellipse takes
+    a class in 1 .. num_classes - 1 (a later ellipse covers an earlier one), the mask is the int64
+    (S,S) label map and a pixel's colour is its class's; the default draws exactly what it always drew."""
+    if num_classes > 1:
+        return _ellipse_labels(rng, size, num_classes)
     yy, xx = np.mgrid[0:size, 0:size].astype(np.float32) + 0.5
     mask = np.zeros((size, size), dtype=bool)
     for _ in range(int(rng.integers(1, 4))):
@@ -29,25 +33,46 @@ def ellipse_sample(rng: np.random.Generator, size: int):
     return img.astype(np.float32), mask[None].astype(np.float32)
 
 
-def ellipse_batch(rng: np.random.Generator, batch: int, size: int):
-    """(images (B,3,S,S), masks (B,1,S,S)) float32 CPU tensors."""
-    pairs = [ellipse_sample(rng, size) for _ in range(batch)]
+def _ellipse_labels(rng: np.random.Generator, size: int, num_classes: int):
+    yy, xx = np.mgrid[0:size, 0:size].astype(np.float32) + 0.5
+    label = np.zeros((size, size), dtype=np.int64)
+    for _ in range(int(rng.integers(1, 4))):
+        cy, cx = rng.uniform(0.2, 0.8, size=2) * size
+        ay, ax = rng.uniform(0.05, 0.25, size=2) * size
+        th = rng.uniform(0.0, np.pi)
+        c, s = np.cos(th), np.sin(th)
+        dy, dx = yy - cy, xx - cx
+        u, v = c * dx + s * dy, -s * dx + c * dy
+        label[(u / ax) ** 2 + (v / ay) ** 2 <= 1.0] = int(rng.integers(1, num_classes))
+    colour = rng.uniform(0.1, 0.9, size=(num_classes, 3)).astype(np.float32)
+    img = colour[label].transpose(2, 0, 1)
+    img = img + rng.normal(0.0, 0.08, size=img.shape).astype(np.float32)
+    img = np.round(np.clip(img, 0.0, 1.0) * 255.0) / 255.0
+    return img.astype(np.float32), label
+
+
+def ellipse_batch(rng: np.random.Generator, batch: int, size: int, num_classes: int = 1):
+    """(images (B,3,S,S), masks (B,1,S,S)) float32 CPU tensors; num_classes > 1: masks (B,S,S) int64 labels."""
+    pairs = [ellipse_sample(rng, size, num_classes) for _ in range(batch)]
     imgs = torch.from_numpy(np.stack([p[0] for p in pairs]))
     masks = torch.from_numpy(np.stack([p[1] for p in pairs]))
     return imgs, masks
 
 
 class SyntheticSegmentation(torch.utils.data.Dataset):
-    """Deterministic map-style dataset: sample i is drawn from ``default_rng(seed + i)``."""
+    """Deterministic map-style dataset: sample i is drawn from ``default_rng(seed + i)``.
+    ``num_classes`` > 1: int64 (S,S) label maps with classes 0 .. num_classes - 1 (ellipse_sample)."""
 
-    def __init__(self, n: int, size: int, seed: int = 1234):
-        self.n, self.size, self.seed = n, size, seed
+    def __init__(self, n: int, size: int, seed: int = 1234, num_classes: int = 1):
+        if int(num_classes) < 1:
+            raise ValueError(f"SyntheticSegmentation: num_classes must be >= 1 (got {num_classes!r})")
+        self.n, self.size, self.seed, self.num_classes = n, size, seed, int(num_classes)
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
-        img, mask = ellipse_sample(np.random.default_rng(self.seed + i), self.size)
+        img, mask = ellipse_sample(np.random.default_rng(self.seed + i), self.size, self.num_classes)
         return torch.from_numpy(img), torch.from_numpy(mask)
 
 
@@ -78,6 +103,16 @@ def resize_bilinear_u8(a: np.ndarray, h: int, w: int) -> np.ndarray:
     top = af[y0][:, x0] * (1 - fx) + af[y0][:, x1] * fx
     bot = af[y1][:, x0] * (1 - fx) + af[y1][:, x1] * fx
     return np.clip(np.floor(top * (1 - fy) + bot * fy + 0.5), 0, 255).astype(np.uint8)   # half up, as cv2
+
+
+def resize_nearest(a: np.ndarray, h: int, w: int) -> np.ndarray:
+    """Nearest-neighbour resize of an HW / HWC array (source index floor((i + 0.5) n / m), as cv2's
+    INTER_NEAREST and PIL's NEAREST pick it): every output value is one of the input's -- what a map
+    of class indices needs."""
+    sh, sw = a.shape[:2]
+    y = np.minimum(((np.arange(h) + 0.5) * (sh / h)).astype(np.int64), sh - 1)
+    x = np.minimum(((np.arange(w) + 0.5) * (sw / w)).astype(np.int64), sw - 1)
+    return a[y][:, x]
 
 
 class AugmentationTransform:
@@ -120,12 +155,16 @@ class AugmentationTransform:
         return image[top:top + nh, left:left + nw], mask[top:top + nh, left:left + nw], image.shape[:2]
 
     @classmethod
-    def apply(cls, image: np.ndarray, mask: np.ndarray, params):
+    def apply(cls, image: np.ndarray, mask: np.ndarray, params, label_mask: bool = False):
+        """label_mask: the mask holds class indices and is resized nearest-neighbour."""
         image, mask, (h, w) = cls.crop(image, mask, params)
-        return resize_bilinear_u8(np.ascontiguousarray(image), h, w), resize_bilinear_u8(np.ascontiguousarray(mask), h, w)
+        image = resize_bilinear_u8(np.ascontiguousarray(image), h, w)
+        if label_mask:
+            return image, resize_nearest(np.ascontiguousarray(mask), h, w)
+        return image, resize_bilinear_u8(np.ascontiguousarray(mask), h, w)
 
-    def __call__(self, image, mask):
-        return self.apply(image, mask, self.draw(*image.shape[:2]))
+    def __call__(self, image, mask, label_mask: bool = False):
+        return self.apply(image, mask, self.draw(*image.shape[:2]), label_mask)
 
 
 class SegmentationDataset(torch.utils.data.Dataset):
@@ -134,15 +173,27 @@ class SegmentationDataset(torch.utils.data.Dataset):
     ``image_size`` read as cv2.resize reads it, i.e. (width, height) (cswin:160-161), optionally augmented, returned as (3, H, W) / (1, H, W) float32
     in [0, 1].  Decoding uses PIL (cv2 is not in this image).  ``device_augment=True`` returns the
     resized uint8 (H, W, 3) image and (H, W) mask instead, for ``DeviceAugment`` to augment and
-    normalise a whole batch on the GPU."""
+    normalise a whole batch on the GPU.
 
-    def __init__(self, image_dir, mask_dir, image_size=(224, 224), augment=False, device_augment=False):
+    ``label_mode=True`` (not in the reference, which is binary): the mask file holds class indices
+    (a palette or greyscale image; a lossless ``<name>.png`` beside the image's name is preferred to
+    the same-named file).  Its raw values are resized nearest-neighbour, augmented nearest-neighbour,
+    and returned as an int64 (H, W) label map for csu.losses.MultiClassSegLoss.  The device
+    augmentation interpolates masks, so ``device_augment=True`` is refused with it."""
+
+    def __init__(self, image_dir, mask_dir, image_size=(224, 224), augment=False, device_augment=False, label_mode=False):
         import glob
         import os
+        if label_mode and device_augment:
+            raise ValueError("SegmentationDataset: label_mode=True cannot be combined with device_augment=True "
+                             "(the device augmentation interpolates the mask bilinearly)")
+        self.label_mode = bool(label_mode)
         self.image_dir, self.mask_dir, self.image_size = image_dir, mask_dir, tuple(image_size)
         self.augment, self.device_augment = augment, device_augment
         self.transform = AugmentationTransform(flip_prob=0.5, rotate_prob=0.25, crop_scale=(0.75, 1.0)) if augment else None
         self.image_paths = sorted(glob.glob(os.path.join(image_dir, "*.jpg")))
+        if self.label_mode:     # label maps usually travel with lossless images
+            self.image_paths = sorted(self.image_paths + glob.glob(os.path.join(image_dir, "*.png")))
         if not self.image_paths:
             raise ValueError(f"no images found in: {image_dir}")
 
@@ -156,6 +207,15 @@ class SegmentationDataset(torch.utils.data.Dataset):
         path = self.image_paths[idx]
         image = np.asarray(Image.open(path).convert("RGB"))
         mpath = os.path.join(self.mask_dir, os.path.basename(path))
+        if self.label_mode:
+            png = os.path.splitext(mpath)[0] + ".png"
+            try:
+                m = Image.open(png if os.path.exists(png) else mpath)
+                mask = np.asarray(m if m.mode in ("P", "L", "I", "I;16") else m.convert("L"))     # raw indices
+            except (FileNotFoundError, OSError):
+                mask = np.zeros(image.shape[:2], dtype=np.uint8)
+            w, h = self.image_size
+            return resize_bilinear_u8(image, h, w), resize_nearest(mask, h, w)
         try:
             mask = np.asarray(Image.open(mpath).convert("L"))
         except (FileNotFoundError, OSError):
@@ -168,8 +228,10 @@ class SegmentationDataset(torch.utils.data.Dataset):
         if self.device_augment:
             return torch.from_numpy(np.ascontiguousarray(image)), torch.from_numpy(np.ascontiguousarray(mask))
         if self.transform is not None:
-            image, mask = self.transform(image, mask)
+            image, mask = self.transform(image, mask, self.label_mode) if self.label_mode else self.transform(image, mask)
         image = torch.from_numpy(np.ascontiguousarray(image).astype(np.float32) / 255.0).permute(2, 0, 1)
+        if self.label_mode:
+            return image, torch.from_numpy(np.ascontiguousarray(mask).astype(np.int64))
         mask = torch.from_numpy(np.ascontiguousarray(mask).astype(np.float32) / 255.0).unsqueeze(0)
         return image, mask
 

@@ -1,4 +1,5 @@
-"""Training criteria for binary segmentation beyond nn.BCELoss: soft Dice, BCE + Dice, Tversky.
+"""Training criteria beyond nn.BCELoss: soft Dice, BCE + Dice, Tversky (binary, ``SegLoss``) and softmax
+cross-entropy + per-class Dice / Tversky on integer label maps (``MultiClassSegLoss``, at the end).
 
 One family, ``SegLoss``:  ``bce * BCE + tversky * mean_r(1 - TI_r)`` on probabilities ``p`` and
 targets ``t`` viewed as rows (one row for the whole batch, or one per image), with
@@ -105,3 +106,172 @@ def bce_dice_loss(bce: float = 1.0, dice: float = 1.0, smooth: float = 1.0, pos_
 def tversky_loss(alpha: float = 0.3, beta: float = 0.7, smooth: float = 1.0, per_sample: bool = False) -> SegLoss:
     """1 - Tversky index; alpha weighs sum p (false positives), beta sum t (false negatives)."""
     return SegLoss(bce=0.0, tversky=1.0, alpha=alpha, beta=beta, smooth=smooth, per_sample=per_sample)
+
+
+class MultiClassSegLoss:
+    """``criterion(logits, target) -> loss``;  ``criterion.loss_stats(logits, target) -> (loss, stats)``
+    for K-class segmentation: softmax cross-entropy plus a per-class soft Tversky / Dice term,
+
+        p = softmax_k(z),
+        CE = sum_pix w[t] (logsumexp(z) - z_t) / sum_pix w[t]                     (whole batch),
+        TP_rc = sum p_c [t = c],  P_rc = sum p_c,  T_rc = sum [t = c]              (row r, class c),
+        TI_rc = (TP + smooth) / ((1 - alpha - beta) TP + alpha P + beta T + smooth),
+        loss = ce * CE + tversky * mean_r mean_{c in C} (1 - TI_rc),
+
+    rows r = the whole batch, or one per image with ``per_sample``; C = all classes, or 1 .. K-1 with
+    ``include_background=False``.  Pixels whose label is ``ignore_index`` contribute to no sum and get
+    a zero gradient.  stats is an fp64 (3, K) tensor [I; Pr; T] of the hard prediction pred = argmax_k z
+    (the lowest index wins a tie) over the batch: I_c = sum [pred = c][t = c], Pr_c = sum [pred = c],
+    T_c = sum [t = c] -- what csu.train turns into per-class and macro Dice / IoU.
+
+    logits: (B, K, H, W), fp32 or bf16 (bf16 goes to the kernel as it is and is upcast in registers;
+    the arithmetic is fp32 with autocast disabled); either memory layout a csu model produces is read
+    in place.  target: (B, H, W) or (B, 1, H, W), int64 or uint8.  A label outside [0, K) that is not
+    ``ignore_index`` is a caller error: it is not checked (a check would synchronise the host) and
+    matches no class.
+
+    The one deliberate difference from ``F.cross_entropy``: when every pixel is ignored (sum w[t] = 0)
+    the CE term and its gradient are 0, not NaN, so a captured training run survives such a batch.
+
+    ce, tversky: the two weights (>= 0, not both 0); alpha, beta >= 0; smooth > 0; class_weight: K
+    weights >= 0 of the CE term or None.  On the GPU with 2 <= K <= 32 the loss, its gradient and the
+    stats come from the fused csu_seg_ce kernels; more classes take the same formula in torch ops on
+    the device.  Hashable by identity."""
+
+    def __init__(self, num_classes: int, ce: float = 1.0, tversky: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
+                 smooth: float = 0.5, class_weight=None, ignore_index: int = -100, per_sample: bool = False,
+                 include_background: bool = True):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, int) or num_classes < 2:
+            raise ValueError(f"MultiClassSegLoss: num_classes must be an integer >= 2 (got {num_classes!r})")
+        for k, v in {"ce": ce, "tversky": tversky, "alpha": alpha, "beta": beta}.items():
+            if not float(v) >= 0.0 or float(v) == float("inf"):
+                raise ValueError(f"MultiClassSegLoss: {k} must be a finite number >= 0 (got {v!r})")
+        if not 0.0 < float(smooth) < float("inf"):
+            raise ValueError(f"MultiClassSegLoss: smooth must be > 0 (got {smooth!r})")
+        if float(ce) == 0.0 and float(tversky) == 0.0:
+            raise ValueError("MultiClassSegLoss: ce and tversky are both zero")
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+            raise ValueError(f"MultiClassSegLoss: ignore_index must be an integer (got {ignore_index!r})")
+        if class_weight is not None:
+            cw = torch.as_tensor(class_weight, dtype=torch.float32).detach().reshape(-1).cpu().clone()
+            if cw.numel() != num_classes or not bool(torch.isfinite(cw).all()) or bool((cw < 0).any()):
+                raise ValueError("MultiClassSegLoss: class_weight must hold num_classes finite weights >= 0")
+            class_weight = cw
+        self.num_classes = num_classes
+        self.ce, self.tversky, self.alpha, self.beta = float(ce), float(tversky), float(alpha), float(beta)
+        self.smooth, self.class_weight, self.ignore_index = float(smooth), class_weight, ignore_index
+        self.per_sample, self.include_background = bool(per_sample), bool(include_background)
+        self._cw = {}
+
+    @property
+    def params(self):
+        """(w_ce, w_tversky, alpha, beta, smooth): the scalar arguments of csu_seg_ce_fwd."""
+        return (self.ce, self.tversky, self.alpha, self.beta, self.smooth)
+
+    def __repr__(self):
+        return (f"MultiClassSegLoss(num_classes={self.num_classes}, ce={self.ce}, tversky={self.tversky}, "
+                f"alpha={self.alpha}, beta={self.beta}, smooth={self.smooth}, class_weight="
+                f"{None if self.class_weight is None else self.class_weight.tolist()}, ignore_index={self.ignore_index}, "
+                f"per_sample={self.per_sample}, include_background={self.include_background})")
+
+    def _weight(self, device):
+        if self.class_weight is None:
+            return None
+        w = self._cw.get(device)
+        if w is None:
+            w = self._cw[device] = self.class_weight.to(device)
+        return w
+
+    def _torch(self, z, t):
+        """The same formula in torch ops, in z's floating dtype: z (B, K, *), t (B, *) int64."""
+        B, K = z.shape[0], z.shape[1]
+        rows = B if self.per_sample else 1
+        z2 = z.reshape(B, K, -1)
+        t2 = t.reshape(B, -1)
+        live = t2 != self.ignore_index
+        tc = torch.where(live, t2, torch.zeros_like(t2))
+        w = self._weight(z.device)
+        w = torch.ones(K, dtype=z.dtype, device=z.device) if w is None else w.to(z.dtype)
+        lsm = torch.log_softmax(z2, 1)
+        wt = w[tc] * live.to(z.dtype)
+        sw = wt.sum()
+        ce = -(lsm.gather(1, tc.unsqueeze(1)).squeeze(1) * wt).sum()
+        ce = torch.where(sw > 0, ce / torch.where(sw > 0, sw, torch.ones_like(sw)), ce * 0.0)
+        lv = live.to(z.dtype).unsqueeze(1)
+        p = lsm.exp() * lv
+        oh = F.one_hot(tc, K).permute(0, 2, 1).to(z.dtype) * lv
+
+        def rk(x):   # (B, K, n) -> (rows, K, n')
+            return x if rows == B else x.permute(1, 0, 2).reshape(1, K, -1)
+
+        p, oh = rk(p), rk(oh)
+        tp, ps, ts = (p * oh).sum(-1), p.sum(-1), oh.sum(-1)
+        den = (1.0 - self.alpha - self.beta) * tp + self.alpha * ps + self.beta * ts + self.smooth
+        one_minus = 1.0 - (tp + self.smooth) / den
+        if not self.include_background:
+            one_minus = one_minus[:, 1:]
+        return self.ce * ce + self.tversky * one_minus.mean()
+
+    def hard_stats(self, z, t):
+        """fp64 (3, K) [I; Pr; T] in torch ops; the first maximum is the prediction."""
+        K = z.shape[1]
+        z2 = z.reshape(z.shape[0], K, -1)
+        t2 = t.reshape(z.shape[0], -1)
+        live = t2 != self.ignore_index
+        m = z2.max(1, keepdim=True).values
+        ar = torch.arange(K, device=z.device).view(1, K, 1)
+        pred = torch.where(z2 == m, ar, torch.full_like(ar, K)).min(1).values     # lowest index of the maximum
+        cls = torch.arange(K, device=z.device).view(K, 1, 1)
+        pm = (pred.unsqueeze(0) == cls) & live.unsqueeze(0)
+        tm = (t2.unsqueeze(0) == cls) & live.unsqueeze(0)
+        f = torch.float64
+        return torch.stack([(pm & tm).sum((1, 2)).to(f), pm.sum((1, 2)).to(f), tm.sum((1, 2)).to(f)])
+
+    def _run(self, logits, target, with_stats):
+        K = self.num_classes
+        if logits.dim() < 3 or logits.shape[1] != K:
+            raise ValueError(f"MultiClassSegLoss: logits (B, {K}, H, W) (got {tuple(logits.shape)})")
+        if target.dim() == logits.dim() and target.shape[1] == 1:
+            target = target[:, 0]
+        if target.dtype not in (torch.int64, torch.uint8) or \
+                tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+            raise ValueError("MultiClassSegLoss: an int64 or uint8 label map (B, H, W) or (B, 1, H, W) of the logits' size")
+        with torch.autocast(logits.device.type, enabled=False):
+            if logits.is_cuda and K <= 32:
+                from . import ops
+                z = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
+                rows = logits.shape[0] if self.per_sample else 1
+                return ops.seg_ce(z, target, self.params, self._weight(logits.device), self.ignore_index, rows,
+                                  self.include_background, with_stats)
+            z, t = logits.float(), target.long()
+            loss = self._torch(z, t)
+            if not with_stats:
+                return loss
+            return loss, self.hard_stats(z.detach(), t)
+
+    def __call__(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return self._run(logits, target, False)
+
+    def loss_stats(self, logits: torch.Tensor, target: torch.Tensor):
+        """The loss and the hard per-class sums (3, K) fp64 of the same pass."""
+        return self._run(logits, target, True)
+
+
+def ce_loss(num_classes: int, class_weight=None, ignore_index: int = -100) -> MultiClassSegLoss:
+    """Softmax cross-entropy (F.cross_entropy's weighted mean) with the per-class metrics of MultiClassSegLoss."""
+    return MultiClassSegLoss(num_classes, ce=1.0, tversky=0.0, class_weight=class_weight, ignore_index=ignore_index)
+
+
+def ce_dice_loss(num_classes: int, ce: float = 1.0, dice: float = 1.0, smooth: float = 1.0, class_weight=None,
+                 ignore_index: int = -100, per_sample: bool = False, include_background: bool = True) -> MultiClassSegLoss:
+    """ce * CE + dice * mean over classes of (1 - Dice_c); smooth is Dice's (numerator and denominator)."""
+    return MultiClassSegLoss(num_classes, ce=ce, tversky=dice, alpha=0.5, beta=0.5, smooth=smooth / 2,
+                             class_weight=class_weight, ignore_index=ignore_index, per_sample=per_sample,
+                             include_background=include_background)
+
+
+def multiclass_dice_loss(num_classes: int, smooth: float = 1e-6, ignore_index: int = -100, per_sample: bool = False,
+                         include_background: bool = True) -> MultiClassSegLoss:
+    """Mean over classes of the soft Dice loss 1 - (2 sum p_c [t = c] + smooth) / (sum p_c + sum [t = c] + smooth)."""
+    return MultiClassSegLoss(num_classes, ce=0.0, tversky=1.0, alpha=0.5, beta=0.5, smooth=smooth / 2,
+                             ignore_index=ignore_index, per_sample=per_sample, include_background=include_background)

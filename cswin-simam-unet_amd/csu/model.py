@@ -509,8 +509,9 @@ class CSWinTransformer(nn.Module):
         return _ln(x, self.norm_up, _compute_dtype(x))
 
     def up_x4(self, x):
-        """CARAFE4 x4 upsampling + 1x1 output conv (cswin:674-682); returns LOGITS only when the
-        fused sigmoid head cannot be used (num_classes != 1)."""
+        """CARAFE4 x4 upsampling + 1x1 output conv (cswin:674-682); returns LOGITS (B, num_classes, 4H,
+        4W), a view of the class-last token GEMM output -- used when the fused sigmoid head cannot be
+        (num_classes != 1) and by set_head('logits')."""
         B, new_HW, C = x.shape
         H = W = int(math.isqrt(new_HW))
         x = self.upsample1(x)                                             # (B, 16 L, 64) tokens
@@ -551,6 +552,17 @@ class CSWinTransformer(nn.Module):
             raise ValueError(f"weight format {fmt!r}")
         self._weight_format = fmt
         self._fp8 = None
+        return self
+
+    def set_head(self, head: str = "sigmoid"):
+        """'sigmoid' (default): forward returns fp32 probabilities, the reference's output (cswin:684-688).
+        'logits': forward returns the (B, num_classes, H, W) logits of the `output` conv in the compute
+        dtype, for any num_classes (1 included) -- what csu.losses.MultiClassSegLoss trains on.  They
+        are a view of the head GEMM's class-last output (up_x4), which the loss kernels read in place.
+        No parameter or state_dict change."""
+        if head not in ("sigmoid", "logits"):
+            raise ValueError(f"head {head!r}")
+        self._head = head
         return self
 
     def forward(self, x):
@@ -614,6 +626,8 @@ class CSWinTransformer(nn.Module):
     def _forward_body(self, x):
         x = self.forward_features(x)
         x = self.forward_up_features(x)
+        if getattr(self, "_head", "sigmoid") == "logits":
+            return self.up_x4(x)
         if self.num_classes == 1:
             B, L, C = x.shape
             H = W = int(math.isqrt(L))

@@ -342,6 +342,8 @@ def _deferrable(*params) -> bool:
         p = _leaf(p)
         if p is None:
             continue
+        if not p.is_leaf:   # a weight computed in the graph (the K-class head's zero-padded `output`
+            return False    # weight): the next backward node reads its gradient at once
         if p.grad is not None or p._backward_hooks:
             return False
         hooks = getattr(p, "_post_accumulate_grad_hooks", None)
@@ -1095,6 +1097,8 @@ def _param_safe(p) -> bool:
     p = _leaf(p)
     if p is None:
         return True
+    if not p.is_leaf:      # its gradient is read by the next backward node, before the join
+        return False
     if p.grad is not None or p._backward_hooks or _uses(p) > 1:
         return False   # (shared weights: the engine would sum the side-stream gradient before the join)
     hooks = getattr(p, "_post_accumulate_grad_hooks", None)
@@ -1423,6 +1427,117 @@ def seg_loss(prob: torch.Tensor, target: torch.Tensor, params, rows: int, with_s
     if len(params) != 6:
         raise ValueError("seg_loss: params = (w_bce, pos_weight, w_tversky, alpha, beta, smooth)")
     return _SegLossFn.apply(prob, target, tuple(params), rows, bool(with_stats))
+
+
+SEG_CE_MAX_CLASSES = 32
+
+
+def _seg_ce_bucket(K: int) -> int:
+    return 4 if K <= 4 else 8 if K <= 8 else 16 if K <= 16 else 32
+
+
+def _seg_ce_layout(z: torch.Tensor):
+    """(z or a contiguous copy, s_b, s_k, s_pix, pad_ok) of (B, K, *spatial) logits: element strides
+    with the spatial dims flattened to one pixel stride.  No copy for the two layouts the project
+    produces (dense NCHW; the class-last view of a token GEMM's output, padded pitch included)."""
+    B, K = z.shape[0], z.shape[1]
+    sp, n = z.stride(-1) if z.dim() > 2 else 1, 1
+    ok = z.stride(0) >= 0 and z.stride(1) >= 1 and sp >= 1
+    for d in range(z.dim() - 1, 1, -1):     # spatial dims collapse to one stride
+        ok = ok and (z.shape[d] == 1 or z.stride(d) == sp * n)
+        n *= z.shape[d]
+    if not ok:
+        z = z.contiguous()
+        sp = 1
+    sb, sk = z.stride(0), z.stride(1)
+    KB = _seg_ce_bucket(K)
+    last = z.storage_offset() + (B - 1) * sb + (n - 1) * sp + KB
+    pad_ok = sk == 1 and sp >= KB and last * z.element_size() <= z.untyped_storage().nbytes()
+    return z, sb, sk, sp, n, bool(pad_ok)
+
+
+class _SegCEFn(torch.autograd.Function):
+    """w_ce * softmax-CE + w_tversky * mean over rows and classes of (1 - Tversky) on K-class logits
+    (B, K, *spatial), fp32 or bf16, in place in either layout (csrc/seg_ce.hip): csu_seg_ce_fwd (one
+    streaming pass over logits and labels + a fixed-order fp64 finish, which also leaves two backward
+    coefficients per (row, class) and 1 / sum w) and csu_seg_ce_bwd (one pass that recomputes the
+    softmax and writes the gradient in the logits' dtype and strides).  params = (w_ce, w_tversky,
+    alpha, beta, smooth).  with_stats: the same pass also returns the hard per-class sums
+    [sum[pred = c][t = c]; sum[pred = c]; sum[t = c]] of pred = argmax (lowest index on a tie) as a
+    non-differentiable fp64 (3, K) tensor."""
+
+    @staticmethod
+    def forward(ctx, z, t, params, cw, ignore_index: int, rows: int, include_background: bool, with_stats: bool = False):
+        B, K = z.shape[0], z.shape[1]
+        z, sb, sk, sp, HW, pad_ok = _seg_ce_layout(z)
+        t = t.contiguous()
+        w_ce, w_tv, alpha, beta, smooth = (float(v) for v in params)
+        dev = z.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        stats = torch.empty(3, K, dtype=torch.float64, device=dev) if with_stats else None
+        coef = torch.empty(2 * rows * K + 1, dtype=torch.float32, device=dev)
+        nws = lib().csu_seg_ce_workspace(B, K, HW)
+        ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        lab = 1 if t.dtype == torch.int64 else 0
+        geom = (B, K, HW, rows, dtype_code(z), sb, sk, sp, int(pad_ok), lab, int(ignore_index), int(include_background))
+        nbytes = B * K * HW * z.element_size() + B * HW * t.element_size()
+        _launch("seg_ce", lambda: lib().csu_seg_ce_fwd(B, K, HW, rows, geom[4], ptr(z), sb, sk, sp, geom[8], lab, ptr(t),
+                                                       geom[10], ptr(cw), w_ce, w_tv, alpha, beta, smooth, geom[11],
+                                                       ptr(loss), ptr(stats), ptr(coef), ptr(ws), nws, stream_ptr(dev)),
+                (12 * K + 30) * B * HW, nbytes, prec="f32")
+        ctx.save_for_backward(z, t, coef, cw)
+        ctx.seg = (geom, w_ce, w_tv, nbytes)
+        if with_stats:
+            ctx.mark_non_differentiable(stats)
+            return loss, stats
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        z, t, coef, cw = ctx.saved_tensors
+        (B, K, HW, rows, dt, sb, sk, sp, pad_ok, lab, ignore, bg), w_ce, w_tv, nbytes = ctx.seg
+        g = g.float().contiguous()
+        # the gradient has the logits' strides (the kernels share one addressing) and their offset
+        # within 16 B, in a buffer of its own that also covers a padded pixel's last bucket
+        es = z.element_size()
+        off = (z.data_ptr() % 16) // es
+        need = (B - 1) * sb + (HW - 1) * sp + max((K - 1) * sk + 1, _seg_ce_bucket(K) if pad_ok else 0)
+        dz = torch.empty(off + need, dtype=z.dtype, device=z.device).as_strided(z.shape, z.stride(), off)
+        _launch("seg_ce_bwd", lambda: lib().csu_seg_ce_bwd(B, K, HW, rows, dt, ptr(z), sb, sk, sp, pad_ok, lab, ptr(t), ignore,
+                                                           ptr(cw), ptr(g), ptr(coef), w_ce, w_tv, bg, ptr(dz),
+                                                           stream_ptr(z.device)),
+                (14 * K + 20) * B * HW, nbytes + B * K * HW * es, prec="f32")
+        return dz, None, None, None, None, None, None, None
+
+
+def seg_ce(logits: torch.Tensor, target: torch.Tensor, params, class_weight: Optional[torch.Tensor] = None,
+           ignore_index: int = -100, rows: int = 1, include_background: bool = True, with_stats: bool = False):
+    """Fused softmax cross-entropy + per-class Tversky loss of device logits (see _SegCEFn).
+    logits (B, K, *spatial) fp32 or bf16 with 2 <= K <= 32, any strides whose spatial dims collapse
+    to one (others are copied); target (B, *spatial) int64 or uint8; params = (w_ce, w_tversky, alpha,
+    beta, smooth); class_weight: fp32 (K,) on the device or None; rows: 1 or B.  with_stats: returns
+    (loss, fp64 (3, K) hard sums)."""
+    require_device(logits, target, class_weight)
+    if logits.dim() < 2 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("seg_ce: fp32 or bf16 logits (B, K, *spatial)")
+    B, K = logits.shape[0], logits.shape[1]
+    if not 2 <= K <= SEG_CE_MAX_CLASSES:
+        raise ValueError(f"seg_ce: 2 <= K <= {SEG_CE_MAX_CLASSES} classes (got {K})")
+    if target.dtype not in (torch.int64, torch.uint8) or tuple(target.shape) != (B,) + tuple(logits.shape[2:]):
+        raise ValueError("seg_ce: int64 or uint8 target of the logits' shape without the class dim")
+    if logits.numel() < 1:
+        raise ValueError("seg_ce: empty logits")
+    rows = int(rows)
+    if rows not in (1, B):
+        raise ValueError("seg_ce: rows must be 1 or the batch size")
+    if len(params) != 5:
+        raise ValueError("seg_ce: params = (w_ce, w_tversky, alpha, beta, smooth)")
+    if class_weight is not None:
+        if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (K,):
+            raise ValueError("seg_ce: class_weight is an fp32 (K,) tensor")
+        class_weight = class_weight.contiguous()
+    return _SegCEFn.apply(logits, target, tuple(params), class_weight, int(ignore_index), rows, bool(include_background),
+                          bool(with_stats))
 
 
 def augment_batch(images: torch.Tensor, masks: torch.Tensor, params) -> Tuple[torch.Tensor, torch.Tensor]:

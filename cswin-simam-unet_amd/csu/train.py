@@ -76,28 +76,66 @@ def _world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+def _is_label_map(outputs, masks) -> bool:
+    """Integer class indices for K-channel outputs: (B, *spatial), or (B, 1, *spatial) against K > 1."""
+    if masks.is_floating_point() or masks.dtype == torch.bool or outputs.dim() < 2:
+        return False
+    return masks.dim() == outputs.dim() - 1 or (masks.dim() == outputs.dim() and masks.shape[1] == 1 and outputs.shape[1] > 1)
+
+
 def _step_stats(loss, outputs, masks):
-    """Per-step sums (loss, sum(p*t), sum(p), sum(t)) of thresholded predictions, on device."""
+    """Per-step sums (loss, sum(p*t), sum(p), sum(t)) of thresholded predictions, on device.
+    Multi-class (an integer label map for K-channel outputs): (loss, I_0..I_K-1, Pr_0.., T_0..) of the
+    hard prediction argmax_k outputs, the lowest index winning a tie -- the row a multi-class
+    criterion's loss_stats gives, without an ignore_index (which only the criterion knows)."""
+    if _is_label_map(outputs, masks):
+        K = outputs.shape[1]
+        t = (masks[:, 0] if masks.dim() == outputs.dim() else masks).reshape(-1).long()
+        o = outputs.detach().reshape(outputs.shape[0], K, -1)
+        ar = torch.arange(K, device=o.device).view(1, K, 1)
+        pred = torch.where(o == o.max(1, keepdim=True).values, ar, torch.full_like(ar, K)).min(1).values.reshape(-1)
+        cls = torch.arange(K, device=o.device).view(K, 1)
+        pm, tm = pred.view(1, -1) == cls, t.view(1, -1) == cls      # comparisons only: no host sync
+        sums = torch.cat([(pm & tm).sum(1), pm.sum(1), tm.sum(1)])
+        return torch.cat([loss.detach().double().view(1), sums.double()])
     preds = (outputs > 0.5).to(torch.float64).reshape(-1)
     t = masks.to(torch.float64).reshape(-1)
     return torch.stack([loss.detach().double(), (preds * t).sum(), preds.sum(), t.sum()])
 
 
-def _epoch_means(stats: List[torch.Tensor], smooth: float = 1e-6):
+def _epoch_means(stats: List[torch.Tensor], smooth: float = 1e-6, per_class: bool = False):
     """Mean over steps of (loss, Dice, IoU) of the GLOBAL batch: the per-step sums of every rank
     are all-reduced once per epoch, so each step's Dice/IoU is the reference's batch-flattened
-    value over the concatenation of all ranks' batches (cswin:692-708, 797-811)."""
+    value over the concatenation of all ranks' batches (cswin:692-708, 797-811).
+    Multi-class rows (1 + 3 K columns: loss, I, Pr, T per class): the sums are totalled over the
+    epoch's steps (and ranks), Dice_c = (2 I_c + smooth) / (Pr_c + T_c + smooth) and IoU_c = (I_c +
+    smooth) / (Pr_c + T_c - I_c + smooth) come from the totals, and the Dice / IoU returned are the
+    macro means over the classes that occur (Pr_c + T_c > 0).  ``per_class``: also returns the two
+    per-class lists (None, None for binary rows)."""
     if not stats:
-        return 0.0, 0.0, 0.0
+        return (0.0, 0.0, 0.0, None, None) if per_class else (0.0, 0.0, 0.0)
     s = torch.stack(stats)
     w = _world()
     if w > 1:
         dist.all_reduce(s, op=dist.ReduceOp.SUM)
         s[:, 0] /= w
+    if s.shape[1] != 4:
+        K = (s.shape[1] - 1) // 3
+        if s.shape[1] != 1 + 3 * K or K < 2:
+            raise ValueError(f"_epoch_means: rows of 4 or 1 + 3 K columns (got {s.shape[1]})")
+        inter, ps, ts = s[:, 1:].sum(0).view(3, K)
+        dice = (2.0 * inter + smooth) / (ps + ts + smooth)
+        iou = (inter + smooth) / (ps + ts - inter + smooth)
+        seen = (ps + ts > 0).to(dice.dtype)
+        n = seen.sum().clamp(min=1.0)
+        out = torch.cat([torch.stack([s[:, 0].mean(), (dice * seen).sum() / n, (iou * seen).sum() / n]), dice, iou]).tolist()
+        res = (out[0], out[1], out[2])
+        return res + (out[3:3 + K], out[3 + K:]) if per_class else res
     inter, ps, ts = s[:, 1], s[:, 2], s[:, 3]
     dice = (2.0 * inter + smooth) / (ps + ts + smooth)
     iou = (inter + smooth) / (ps + ts - inter + smooth)
-    return float(s[:, 0].mean()), float(dice.mean()), float(iou.mean())
+    res = (float(s[:, 0].mean()), float(dice.mean()), float(iou.mean()))
+    return res + (None, None) if per_class else res
 
 
 def _autocast(device, amp_dtype):
@@ -195,8 +233,8 @@ class _GraphedEval:
             loss, st = bce_loss_stats(out, self.t)
             return torch.cat([loss.detach().double().view(1), st.double()])
         if hasattr(self.crit, "loss_stats"):     # csu.losses.SegLoss: loss + sums from one fused pass
-            loss, st = self.crit.loss_stats(out, self.t)
-            return torch.cat([loss.detach().double().view(1), st.double()])
+            loss, st = self.crit.loss_stats(out, self.t)      # stats of any shape ((3, K) multi-class)
+            return torch.cat([loss.detach().double().view(1), st.double().reshape(-1)])
         return _step_stats(self.crit(out, self.t), out, self.t)
 
     def __call__(self, x, t):
@@ -207,11 +245,15 @@ class _GraphedEval:
         return self.stats.clone()
 
 
-def evaluate_model(model, data_loader, criterion, device, amp_dtype=None, graph=None):
+def evaluate_model(model, data_loader, criterion, device, amp_dtype=None, graph=None, per_class=False):
     """eval mode, no grad; mean over batches of (loss, Dice, IoU) (cswin:712-747).  ``amp_dtype``
     (not in the reference): run the forward under autocast (e.g. torch.bfloat16).  ``graph``
     (None = automatic on a GPU): batches of the first batch's shape replay one captured HIP graph
-    of the forward + loss + metric sums; other shapes (a ragged last batch) run eagerly."""
+    of the forward + loss + metric sums; other shapes (a ragged last batch) run eagerly.
+    Multi-class (integer label maps, a criterion such as csu.losses.MultiClassSegLoss on a
+    ``set_head("logits")`` model): Dice and IoU are the macro means over the classes that occur, from
+    the per-class sums of the whole loader (_epoch_means); ``per_class=True`` returns the per-class
+    Dice and IoU lists after the triple (None, None for a binary run)."""
     model.eval()
     use_graph = (graph is not False and torch.device(device).type == "cuda" and torch.cuda.is_available()
                  and not isinstance(model, torch.nn.parallel.DistributedDataParallel)
@@ -231,25 +273,45 @@ def evaluate_model(model, data_loader, criterion, device, amp_dtype=None, graph=
                 continue
             with _autocast(images.device, amp_dtype):
                 outputs = model(images)
-            stats.append(_step_stats(criterion(outputs, masks), outputs, masks))
-    return _epoch_means(stats)
+            stats.append(_eager_stats(criterion, outputs, masks))
+    return _epoch_means(stats, per_class=per_class)
+
+
+def _multiclass_stats(criterion, outputs, masks) -> bool:
+    """A multi-class criterion's own loss_stats supplies the step's sums outside a graph too (it
+    alone knows the ignore_index); the binary criteria take _step_stats as before."""
+    return hasattr(criterion, "loss_stats") and _is_label_map(outputs, masks)
+
+
+def _eager_stats(criterion, outputs, masks):
+    if _multiclass_stats(criterion, outputs, masks):
+        loss, st = criterion.loss_stats(outputs, masks)
+        return torch.cat([loss.detach().double().view(1), st.double().reshape(-1)])
+    return _step_stats(criterion(outputs, masks), outputs, masks)
 
 
 def train_step(model, images, masks, criterion, optimizer, reducer=None, amp_dtype=None):
     """One reference step (cswin:779-794): zero_grad, forward, loss, backward, optimizer step.
     ``reducer``: a ``csu.dist.GradAllReduce`` averaging the gradients across ranks (instead of DDP).
     ``amp_dtype``: forward under autocast (the loss stays fp32).
-    Returns the device tensor of per-step sums (loss, sum(p*t), sum(p), sum(t)) -- no host sync."""
+    Returns the device tensor of per-step sums (loss, sum(p*t), sum(p), sum(t)) -- no host sync;
+    for integer label maps (loss, I_c.., Pr_c.., T_c..) per class, see _step_stats."""
     optimizer.zero_grad(set_to_none=True)
     with _autocast(images.device, amp_dtype):
         outputs = model(images)
-    loss = criterion(outputs, masks)
+    st = None
+    if _multiclass_stats(criterion, outputs, masks):
+        loss, st = criterion.loss_stats(outputs, masks)
+    else:
+        loss = criterion(outputs, masks)
     loss.backward()
     if reducer is not None:
         reducer.finish()
     _clip_for(optimizer)
     optimizer.step()
     with torch.no_grad():
+        if st is not None:
+            return torch.cat([loss.detach().double().view(1), st.double().reshape(-1)])
         return _step_stats(loss, outputs, masks)
 
 
@@ -314,7 +376,7 @@ class _GraphedTrain:
                                        metrics=self.crit is bce_loss or hasattr(self.crit, "loss_stats"))
         loss, out = self.gs(images, masks)
         if self.gs.stats is not None:
-            return torch.cat([loss.double().view(1), self.gs.stats.double()])
+            return torch.cat([loss.double().view(1), self.gs.stats.double().reshape(-1)])
         with torch.no_grad():
             return _step_stats(loss, out, self.gs.t)
 
@@ -336,7 +398,10 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     Gradient clipping: an optimizer with ``max_grad_norm`` / ``skip_nonfinite`` (make_optimizer) adds
     two history keys, ``grad_norm`` (per-epoch mean of the per-step pre-clip global norm over the steps
     with a finite norm) and ``skipped_steps`` (per-epoch count of skipped non-finite steps), from
-    device scalars read once per epoch; without the options the history has the reference's keys."""
+    device scalars read once per epoch; without the options the history has the reference's keys.
+    Multi-class (integer label maps): ``train_dice`` / ``train_iou`` / ``test_dice`` / ``test_iou`` are the
+    macro means over the classes that occur, and four more keys, ``train_class_dice``, ``train_class_iou``,
+    ``test_class_dice`` and ``test_class_iou``, hold a list of K per-class values per epoch."""
     history = {"train_loss": [], "train_dice": [], "train_iou": [], "test_loss": [], "test_dice": [], "test_iou": [],
                "learning_rates": []}
     clips = _clips(optimizer)
@@ -349,6 +414,9 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
         start, past = load_checkpoint(resume_from, model, optimizer, scheduler, map_location=device)
         for k in history:
             history[k] = list(past.get(k, []))
+        for k in ("train_class_dice", "train_class_iou", "test_class_dice", "test_class_iou"):
+            if k in past:
+                history[k] = list(past[k])
     use_graph = graph is not False and _graphable(model, optimizer, device, criterion)
     if graph and not use_graph:
         raise ValueError("train_model(graph=True) needs a csu model on a GPU and csu.optim.FusedAdamW")
@@ -380,13 +448,13 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
                 stats.append(train_step(model, images, masks, criterion, optimizer, reducer, amp_dtype=amp_dtype))
             if clips and isinstance(getattr(optimizer, "grad_norm", None), torch.Tensor):
                 norms.append(optimizer.grad_norm.detach().clone())   # the optimizer rewrites it in place
-        train_loss, train_dice, train_iou = _epoch_means(stats)
+        train_loss, train_dice, train_iou, train_cd, train_ci = _epoch_means(stats, per_class=True)
         if clips:
             gn, sk = _clip_epoch(norms, optimizer, skipped0)
             history["grad_norm"].append(gn)
             history["skipped_steps"].append(sk)
-        test_loss, test_dice, test_iou = evaluate_model(model, test_loader, criterion, device, amp_dtype=amp_dtype,
-                                                        graph=use_graph)
+        test_loss, test_dice, test_iou, test_cd, test_ci = evaluate_model(model, test_loader, criterion, device,
+                                                                          amp_dtype=amp_dtype, graph=use_graph, per_class=True)
         if scheduler is not None:
             scheduler.step(test_loss)
             if hasattr(optimizer, "sync_lr"):   # FusedAdamW: the device lr a captured step reads
@@ -394,6 +462,10 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
         current_lr = optimizer.param_groups[0]["lr"]
         for k, v in zip(history, (train_loss, train_dice, train_iou, test_loss, test_dice, test_iou, current_lr)):
             history[k].append(v)
+        for k, v in (("train_class_dice", train_cd), ("train_class_iou", train_ci), ("test_class_dice", test_cd),
+                     ("test_class_iou", test_ci)):
+            if v is not None:       # multi-class runs only: a binary history keeps exactly its keys
+                history.setdefault(k, []).append(v)
         if checkpoint_path is not None:
             from .report import save_checkpoint
             save_checkpoint(checkpoint_path, model, optimizer, scheduler, epoch + 1, history)

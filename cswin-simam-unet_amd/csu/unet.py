@@ -185,6 +185,15 @@ class UNet(nn.Module):
         self.outc = nn.Conv2d(64, n_classes, kernel_size=1)
         self.sigmoid = nn.Sigmoid()
 
+    def set_head(self, head: str = "sigmoid"):
+        """'sigmoid' (default): NCHW fp32 probabilities (unet:250).  'logits': the (B, n_classes, H, W)
+        logits of `outc` in the compute dtype, a view of its class-last (NHWC) output that
+        csu.losses.MultiClassSegLoss reads in place.  No parameter or state_dict change."""
+        if head not in ("sigmoid", "logits"):
+            raise ValueError(f"head {head!r}")
+        self._head = head
+        return self
+
     def forward(self, x):
         x = x.permute(0, 2, 3, 1)                      # NHWC view of the image
         x1 = self.inc(x)
@@ -197,4 +206,6 @@ class UNet(nn.Module):
         x = self.up3(x, x2)
         x = self.up4(x, x1)
         logits = ops.conv2d(x, self.outc.weight, self.outc.bias, 1, 0)   # (B, H, W, n_classes)
+        if getattr(self, "_head", "sigmoid") == "logits":
+            return logits.permute(0, 3, 1, 2)
         return self.sigmoid(logits.float()).permute(0, 3, 1, 2)

@@ -792,6 +792,45 @@ int csu_seg_loss_bwd(long n, int rows, const float* p, const float* t, const flo
                      float w_bce, float pos_weight, float w_tversky, float* dp, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fused multi-class segmentation loss (csrc/seg_ce.hip): softmax cross-entropy + per-class
+ * Tversky (Dice is alpha = beta = 0.5) on K-class logits and integer labels.  The reference has no
+ * counterpart: it trains num_classes=1 with nn.BCELoss (cswin:924, 936).
+ *   z: logits of B images x K classes x HW pixels, dtype CSU_F32 or CSU_BF16 (upcast in registers),
+ *      element (b, k, pix) at z[b s_b + k s_k + pix s_pix]; class-last (s_k = 1, s_pix = pitch >= K)
+ *      and NCHW (s_pix = 1) are read with vector loads, anything else per element.  pad_ok != 0:
+ *      with s_k = 1 and s_pix >= KB (K rounded up to 4, 8, 16 or 32) the KB elements from every
+ *      pixel's start lie inside the allocation (a [..., :K] view of a padded GEMM output) and may be
+ *      read (dz: written, as zeros).
+ *   t: labels, B x HW contiguous, label_dtype 0 = uint8, 1 = int64.  A pixel with t == ignore_index
+ *      contributes to no sum and gets a zero gradient; other labels outside [0, K) are a caller
+ *      error (they match no class; no label indexes memory).
+ *   p = softmax_k(z) in fp32; rows = 1 (one Tversky row for the batch) or B (one per image):
+ *   CE = sum_pix w[t] (logsumexp(z) - z_t) / sum_pix w[t]   (w = class_weight, NULL: 1); 0, with a
+ *        zero gradient, when every pixel is ignored (F.cross_entropy gives NaN there);
+ *   TP_rc = sum p_c [t = c], P_rc = sum p_c, T_rc = sum [t = c], D = (1 - alpha - beta) TP + alpha P + beta T + smooth,
+ *   loss[0] = w_ce CE + w_tversky mean_r mean_{c in C} (1 - (TP + smooth) / D),  C = all classes, or
+ *        1 .. K-1 with include_background = 0.  Deterministic (fixed-order sums, no atomics).
+ * fwd also writes coef (csu_seg_ce_coef_floats = 2 rows K + 1 floats: per (row, class) A = (D - (TP +
+ * smooth)(1 - alpha - beta)) / D^2 and C = alpha (TP + smooth) / D^2, zero for an excluded background;
+ * then 1 / sum w) and, with stats != NULL, the fp64 (3, K) hard sums over the batch of pred =
+ * argmax_k z (lowest index wins a tie): stats[c] = sum [pred = c][t = c], stats[K + c] = sum [pred = c],
+ * stats[2 K + c] = sum [t = c].  Workspace csu_seg_ce_workspace(B, K, HW) bytes (0: bad arguments).
+ * bwd: dz_k = dloss[0] (w_ce w[t] (p_k - [k = t]) / sum w
+ *                      - (w_tversky / (rows |C|)) p_k (G_k - sum_c G_c p_c)),  G_c = A_rc [t = c] - C_rc,
+ * written in the logits' dtype with the logits' strides.
+ * CSU_E_ARG: B or HW < 1, K < 2 or K > 32, rows not 1 or B, a dtype other than the above, a stride
+ * < 1, smooth <= 0, a negative weight, alpha or beta, both weights zero, a null pointer.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_seg_ce_workspace(int B, int K, long HW);
+int csu_seg_ce_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix, int pad_ok,
+                   int label_dtype, const void* t, long ignore_index, const float* class_weight, float w_ce,
+                   float w_tversky, float alpha, float beta, float smooth, int include_background, float* loss,
+                   double* stats, float* coef, void* workspace, size_t ws_bytes, void* stream);
+int csu_seg_ce_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix, int pad_ok,
+                   int label_dtype, const void* t, long ignore_index, const float* class_weight, const float* dloss,
+                   const float* coef, float w_ce, float w_tversky, int include_background, void* dz, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mask-aligned batch augmentation (AugmentationTransform cswin:20-87 + the dataset's /255 and
  * HWC -> CHW, cswin:166-173), square S x S images: img uint8 (B, S, S, 3), mask uint8 (B, S, S),
  * params int32 (B, 7) on the device = {hflip, vflip, clockwise quarter turns 0..3, crop top,
