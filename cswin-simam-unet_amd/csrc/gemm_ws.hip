@@ -55,6 +55,10 @@ struct WsLnF {
 // C = N features) runs the LayerNorm backward on it -- dx = dres + rstd (g - mean(g) - xhat
 // mean(g xhat)), g = dh * gamma -- and writes dx (fp32) + its bf16 copy and the block's dgamma / dbeta
 // column partials (row blockIdx.x of part [M / 64][2C], csu_layernorm_param_reduce_batch's layout).
+// dh is rounded to bf16 exactly as the plain epilogue would store it (the unfused path's numerics), the
+// tiles meet in LDS, and each wave then handles whole token rows like ln_bwd (layernorm.hip): row sums
+// inside the wave, row-contiguous stores, fixed summation order.  The x / dres rows are loaded during the
+// main loop, a few per weight unit (after the last MFMA one workgroup per CU has nothing to hide them).
 struct WsLn {
     const float* x;      // LayerNorm input (M, C) fp32
     const float* gamma;  // (C)
@@ -102,8 +106,32 @@ __device__ __forceinline__ bf16x8 e4m3x8_bf16(u32x2 w) {
     return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
+// WS_LNBWD row phase: the sum over the LPR = 32 / 64 lanes of a token row, on the VALU (DPP within the
+// 16-lane rows, the permlane swaps across them), every lane gets the sum; fixed association
+template <int LPR> __device__ __forceinline__ float ln_row_sum(float x) {
+    x = sum8_dpp(x);
+    x += dppf<0x128>(x);   // row_ror:8: lane i <- i ^ 8 of its 16-lane row
+    x = xsum16(x);
+    if constexpr (LPR == 64) x = xsum32(x);
+    return x;
+}
+// lane j (< 16) of v holds the value of the wave's row j: that of the lane's row RPI i + lane / (64 / RPI)
+template <int RPI> __device__ __forceinline__ float ln_row_val(float v, int i, int lane) {
+    const int b = __builtin_bit_cast(int, v);
+    if constexpr (RPI == 1) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, i));
+    else {
+        const int lo = __builtin_amdgcn_readlane(b, 2 * i), hi = __builtin_amdgcn_readlane(b, 2 * i + 1);
+        return __builtin_bit_cast(float, lane < 32 ? lo : hi);
+    }
+}
+
+// WS_LNBWD's LDS beside the token panel is its bf16 dh tile [64][N + 4] only; at N = 128 two workgroups
+// fit a CU's LDS and registers, so one's row phase runs beside the other's main loop
+constexpr int ws_ep_floats(int n, int epi) { return epi == WS_LNBWD ? WS_BM * (n + 4) / 2 : 4 * WS_BM * 36; }
+constexpr int ws_occ(int n, int epi, int ns) { return ws_wn(n) < 4 || ns > 1 || (epi == WS_LNBWD && n <= 128) ? 2 : 1; }
+
 template <int K, int N, int EPI, typename TOUT, int NS = 1, int F8 = 0>
-__global__ __launch_bounds__(256, ws_wn(N) < 4 || NS > 1 ? 2 : 1) void gemm_ws_kernel(long M, const bf16* __restrict__ X, int ldx,
+__global__ __launch_bounds__(256, ws_occ(N, EPI, NS)) void gemm_ws_kernel(long M, const bf16* __restrict__ X, int ldx,
                                                       const bf16* __restrict__ Wf, const float* __restrict__ bias,
                                                       const float* __restrict__ resid, TOUT* __restrict__ out,
                                                       WsLn ln = WsLn{}, WsLnF lnf = WsLnF{},
@@ -124,14 +152,15 @@ __global__ __launch_bounds__(256, ws_wn(N) < 4 || NS > 1 ? 2 : 1) void gemm_ws_k
     constexpr int XS = K + 8;                      // LDS row stride of the token panel (bf16)
     constexpr int ES = 36;                         // fp32 row stride of the epilogue region
     __shared__ __attribute__((aligned(16))) bf16 xs[XLDS ? WS_BM * XS : 8];
-    __shared__ __attribute__((aligned(16))) float ep_all[4 * WS_BM * ES];
+    static_assert(ES == 36, "ws_ep_floats");
+    __shared__ __attribute__((aligned(16))) float ep_all[ws_ep_floats(N, EPI)];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wn = wave % WN;                      // this wave's N slot
     const int r = lane & 31, h = lane >> 5;
     const long m0 = (long)blockIdx.x * ws_tokens(N) + WS_BM * (wave / WN);   // the wave's 64-token panel
-    float* ep = ep_all + wave * WS_BM * ES;
+    float* ep = ep_all + (EPI == WS_LNBWD ? 0 : wave * WS_BM * ES);   // the wave's region (WS_LNBWD: one tile, dht)
 
     // tile order rotated per workgroup (its index within the XCD: ids x, x + 8, ... run on XCD x), so
     // the CUs of an XCD do not all read the same weight lines at the same moment
@@ -205,7 +234,23 @@ __global__ __launch_bounds__(256, ws_wn(N) < 4 || NS > 1 ? 2 : 1) void gemm_ws_k
     static_assert(EPI != WS_RESID_LN || !BF, "gemm_ws: the LayerNorm epilogue writes the fp32 residual stream");
     float bv[8], rv[8][4], sv[8];
     const auto rs_s = buf_rsrc(wsc, F8 == 1 ? (long)N * 4 : 0);
-    f32x16 keep[EPI == WS_LNBWD ? NT : 1][2];
+    // WS_LNBWD: the row phase's layout (wave w: token rows 16 w .. 16 w + 15, LN_LPR lanes x 4 features
+    // per row, LN_RPI rows per wave instruction) and its operands.  The x / dres rows (px, pr) are
+    // loaded in the row layout DURING the main loop, LN_PPU loads at the start of every unit: they sit
+    // behind that unit's weight loads in vmcnt's order and in front of the next unit's, which are not
+    // waited for until a whole unit of MFMAs later.  dht: the workgroup's dh tile in LDS, bf16.
+    constexpr bool LNB = EPI == WS_LNBWD;
+    constexpr int LN_LPR = LNB ? N / 4 : 64, LN_RPI = 64 / LN_LPR, LN_NI = 16 / LN_RPI;
+    constexpr int LN_PPU = (2 * LN_NI + U - 1) / U;   // row loads per unit
+    constexpr int LN_DS = N + 4;                      // bf16 row stride of dht (8-B lane writes: 2 r + h banks)
+    static_assert(!LNB || (LN_LPR == 32 || LN_LPR == 64), "gemm_ws: the row phase holds C = 128 or 256");
+    static_assert(!LNB || WS_BM * LN_DS * 2 <= (int)sizeof(ep_all), "gemm_ws: the dh tile must fit the epilogue region");
+    static_assert(!LNB || (XLDS && 8 * N * 4 <= (int)sizeof(xs)), "gemm_ws: the column partials reuse the token panel");
+    bf16* dht = reinterpret_cast<bf16*>(ep_all);
+    const int ln_c0 = 4 * (lane % LN_LPR);
+    float px[LNB ? LN_NI : 1][4], pr[LNB ? LN_NI : 1][4], ln_gw[4], ln_mu = 0.f, ln_rs = 0.f;
+    const auto rs_lx = buf_rsrc(LNB ? ln.x + m0 * N : nullptr, LNB ? (M - m0) * N * 4 : 0);
+    const auto rs_lr = buf_rsrc(LNB && ln.dres ? ln.dres + m0 * N : nullptr, LNB && ln.dres ? (M - m0) * N * 4 : 0);   // null: reads 0
     float yk[EPI == WS_RESID_LN ? NT : 1][8][4];   // y of the wave's tiles in the store layout (LayerNorm)
     float lg[EPI == WS_RESID_LN ? NT : 1][4], lb[EPI == WS_RESID_LN ? NT : 1][4];
     if constexpr (EPI == WS_RESID_LN) {   // gamma / beta of the lane's 4 features of each tile
@@ -219,6 +264,22 @@ __global__ __launch_bounds__(256, ws_wn(N) < 4 || NS > 1 ? 2 : 1) void gemm_ws_k
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int c = u % CH;
+        if constexpr (LNB) {
+            if (u == 0) {
+                load4(ln.gamma + ln_c0, ln_gw);
+                ln_mu = ln.mean[m0 + 16 * wave + (lane & 15)];
+                ln_rs = ln.rstd[m0 + 16 * wave + (lane & 15)];
+            }
+#pragma unroll
+            for (int j = 0; j < LN_PPU; ++j) {
+                const int p = u * LN_PPU + j, i = p >> 1;
+                if (p < 2 * LN_NI) {
+                    const unsigned off = (unsigned)((16 * wave + LN_RPI * i + lane / LN_LPR) * N + ln_c0) * 4;
+                    if (p & 1) buf_ld4(rs_lr, off, pr[i]);
+                    else buf_ld4(rs_lx, off, px[i]);
+                }
+            }
+        }
         if (EPI != WS_LNBWD && c == CH - 1) {
             const int n0 = 32 * (wn + WN * tile_of(u / CH));
             if constexpr (BF) {
@@ -263,8 +324,17 @@ __global__ __launch_bounds__(256, ws_wn(N) < 4 || NS > 1 ? 2 : 1) void gemm_ws_k
         __builtin_amdgcn_sched_barrier(0);
         if (c != CH - 1) continue;
         if constexpr (EPI == WS_LNBWD) {
-            keep[u / CH][0] = a0;
-            keep[u / CH][1] = a1;
+            // the finished tile, rounded to bf16 as the plain epilogue stores it, into its columns of dht
+            const int n0 = 32 * (wn + WN * tile_of(u / CH));
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const f32x16& a = t ? a1 : a0;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float v[4] = {a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]};
+                    store4(dht + (32 * t + r) * LN_DS + n0 + 8 * g + 4 * h, v);
+                }
+            }
             a0 = f32x16{};
             a1 = f32x16{};
             continue;
@@ -374,119 +444,59 @@ __global__ __launch_bounds__(256, ws_wn(N) < 4 || NS > 1 ? 2 : 1) void gemm_ws_k
         }
     }
     if constexpr (EPI == WS_LNBWD) {
-        // lane (r, h) holds dh of tokens r (t = 0) and 32 + r (t = 1), features
-        // 32 nt(i) + 8 g + 4 h + e of its tiles i.  Pass 1: xhat, g = dh gamma, the token sums of g and
-        // g xhat (lane -> half pair by a shuffle -> the 4 waves through LDS in wave order) and the
-        // column partials of dh xhat / dh over the 64 tokens.  Pass 2: dx.
-        constexpr int C = N;
-        const auto rs_x = buf_rsrc(ln.x + m0 * C, (M - m0) * C * 4);
-        const auto rs_r = buf_rsrc(ln.dres ? ln.dres + m0 * C : nullptr, ln.dres ? (M - m0) * C * 4 : 0);
-        float mu[2], rs[2];
+        // ---- row phase: every wave's tiles are in dht (bf16, the plain epilogue's rounding); after the
+        // barrier the token panel xs is dead too.  Wave w owns rows 16 w .. 16 w + 15 whole: lane
+        // (q, c0) of LN_LPR lanes per row, the arithmetic of ln_bwd (layernorm.hip) on prefetched rows.
+        __syncthreads();
+        const auto rs_dx = buf_rsrc(ln.dx + m0 * N, (M - m0) * N * 4);
+        const auto rs_dxb = buf_rsrc(ln.dxb + m0 * N, (M - m0) * N * 2);
+        float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            mu[t] = ln.mean[m0 + 32 * t + r];
-            rs[t] = ln.rstd[m0 + 32 * t + r];
+        for (int i = 0; i < LN_NI; ++i) {
+            const int q = LN_RPI * i + lane / LN_LPR;   // row within the wave's 16
+            float dh[4], xh[4], gg[4], o[4];
+            load4(dht + (16 * wave + q) * LN_DS + ln_c0, dh);
+            const float mu = ln_row_val<LN_RPI>(ln_mu, i, lane), rs = ln_row_val<LN_RPI>(ln_rs, i, lane);
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                xh[e] = (px[i][e] - mu) * rs;
+                gg[e] = dh[e] * ln_gw[e];
+                s1 += gg[e];
+                s2 += gg[e] * xh[e];
+                dg[e] += dh[e] * xh[e];
+                db[e] += dh[e];
+            }
+            s1 = ln_row_sum<LN_LPR>(s1) / N;
+            s2 = ln_row_sum<LN_LPR>(s2) / N;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = rs * (gg[e] - s1 - xh[e] * s2) + pr[i][e];
+            const unsigned off = (unsigned)((16 * wave + q) * N + ln_c0);
+            buf_st4(rs_dx, off * 4, o);
+            buf_st4bf(rs_dxb, off * 2, o);
         }
-        float xh[NT][2][16], gam[NT][16];
-        float rv2[NT][2][16];
+        // column partials: the wave's row halves (C = 128), then the 4 waves in wave order through LDS
+        float* red = reinterpret_cast<float*>(xs);   // [4 waves][2][C]
+        if constexpr (LN_RPI == 2) {
 #pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int n0 = 32 * (wn + WN * tile_of(i));
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                load4(ln.gamma + n0 + 8 * g + 4 * h, gam[i] + 4 * g);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const unsigned off = (unsigned)((32 * t + r) * C + n0 + 8 * g + 4 * h) * 4;
-                    buf_ld4(rs_x, off, xh[i][t] + 4 * g);
-                    buf_ld4(rs_r, off, rv2[i][t] + 4 * g);
-                }
+            for (int e = 0; e < 4; ++e) {
+                dg[e] += __shfl_xor(dg[e], 32, 64);
+                db[e] += __shfl_xor(db[e], 32, 64);
             }
         }
-        float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-        float dgc[NT][16], dbc[NT][16];
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                dgc[i][j] = 0.f;
-                dbc[i][j] = 0.f;
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const float dh = keep[i][t][j];
-                    const float x_h = (xh[i][t][j] - mu[t]) * rs[t];
-                    xh[i][t][j] = x_h;
-                    const float gg = dh * gam[i][j];
-                    s1[t] += gg;
-                    s2[t] += gg * x_h;
-                    dgc[i][j] += dh * x_h;
-                    dbc[i][j] += dh;
-                }
-            }
-        float* lnx = ep_all;   // [4 waves][2 sums][64 tokens]
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            s1[t] += __shfl_xor(s1[t], 32, 64);
-            s2[t] += __shfl_xor(s2[t], 32, 64);
-            if (h == 0) {
-                lnx[(wave * 2 + 0) * 64 + 32 * t + r] = s1[t];
-                lnx[(wave * 2 + 1) * 64 + 32 * t + r] = s2[t];
-            }
+        if (lane < LN_LPR) {
+            store4(red + (wave * 2 + 0) * N + ln_c0, dg);
+            store4(red + (wave * 2 + 1) * N + ln_c0, db);
         }
         __syncthreads();
-        float S1[2], S2[2];
+        float* prow = ln.part + (size_t)blockIdx.x * 2 * N;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            S1[t] = S2[t] = 0.f;
+        for (int i = threadIdx.x; i < 2 * N; i += 256) {
+            const int k = i / N, c = i % N;
+            float s = 0.f;
 #pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                S1[t] += lnx[(w * 2 + 0) * 64 + 32 * t + r];
-                S2[t] += lnx[(w * 2 + 1) * 64 + 32 * t + r];
-            }
-            S1[t] *= 1.f / C;
-            S2[t] *= 1.f / C;
-        }
-        const auto rs_dx = buf_rsrc(ln.dx + m0 * C, (M - m0) * C * 4);
-        const auto rs_dxb = buf_rsrc(ln.dxb + m0 * C, (M - m0) * C * 2);
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int n0 = 32 * (wn + WN * tile_of(i));
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int j = 4 * g + e;
-                        o[e] = rs[t] * (keep[i][t][j] * gam[i][j] - S1[t] - xh[i][t][j] * S2[t]) + rv2[i][t][j];
-                    }
-                    const unsigned off = (unsigned)((32 * t + r) * C + n0 + 8 * g + 4 * h);
-                    buf_st4(rs_dx, off * 4, o);
-                    buf_st4bf(rs_dxb, off * 2, o);
-                }
-        }
-        // column partials: the 32 token lanes of each half (xor tree), then lanes r = 0 write the row
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1)
-#pragma unroll
-            for (int i = 0; i < NT; ++i)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    dgc[i][j] += __shfl_xor(dgc[i][j], o, 64);
-                    dbc[i][j] += __shfl_xor(dbc[i][j], o, 64);
-                }
-        if (r == 0) {
-            float* prow = ln.part + (size_t)blockIdx.x * 2 * C;
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                const int n0 = 32 * (wn + WN * tile_of(i));
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    store4(prow + n0 + 8 * g + 4 * h, dgc[i] + 4 * g);
-                    store4(prow + C + n0 + 8 * g + 4 * h, dbc[i] + 4 * g);
-                }
-            }
+            for (int w = 0; w < 4; ++w) s += red[(w * 2 + k) * N + c];
+            prow[i] = s;
         }
     }
 }

@@ -2655,8 +2655,9 @@ class _LnLinearWsFn(torch.autograd.Function):
     + b) for CSWinBlock's norm1 -> qkv (cswin:357 -> cswin:337) at C = 128 / 256.  Forward: the
     LayerNorm (or the values the producing fused Mlp already computed, _ln_pre) and csu_gemm_ws.
     Backward: ONE csu_gemm_ws_lnbwd launch computes dh = dY W and runs the norm1 backward on it in
-    its epilogue (dx = dres + LN'(dh), its bf16 copy and the dgamma / dbeta block partials) -- dh
-    never reaches HBM and the LayerNorm-backward launch is gone; dW / db of the Linear as _LinearFn."""
+    its epilogue (dx = dres + LN'(bf16(dh)), its bf16 copy and the dgamma / dbeta block partials) -- dh
+    never reaches HBM and the LayerNorm-backward launch is gone; dW / db of the Linear as _LinearFn.
+    The ledger charges the fused launch to "gemm": "layernorm_bwd" falls and "gemm" rises by it."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, weight, bias, eps: float, wf, wtf, pre):
@@ -2705,7 +2706,9 @@ class _LnLinearWsFn(torch.autograd.Function):
         _launch("gemm", lambda: lib().csu_gemm_ws_lnbwd(rows, C, N, ptr(dy2), ptr(wtf), ptr(x), ptr(g), ptr(mean), ptr(rstd),
                                                        ptr(dres_k), ptr(dx), ptr(dxb), ptr(work), stream_ptr(x.device)),
                 2 * rows * N * C + 12 * rows * C,
-                rows * N * 2 + N * C * 2 + rows * C * (4 + (4 if dres_k is not None else 0) + 4 + 2) + rows * 8,
+                # read once: dy, the weight, x, dres, gamma, mean / rstd; written once: dx, its bf16 copy, part
+                rows * N * 2 + N * C * 2 + rows * C * (4 + (4 if dres_k is not None else 0)) + C * 4 + rows * 8
+                + rows * C * (4 + 2) + work.numel() * 4,
                 prec="bf16", tag=f"{rows}x{C}x{N}:lnbwd:ws")
         dgb = _grad_dest(ctx.params)
         if dgb is None:
@@ -2727,7 +2730,9 @@ class _LnLinearWsFn(torch.autograd.Function):
 
 
 # the norm1 -> qkv pair on csu_gemm_ws with the LayerNorm backward in the input-gradient GEMM
-FUSE_LN_QKV = False   # measured: the epilogue phase costs what the LayerNorm launch saved
+# (csu_gemm_ws_lnbwd: dh is never written and the norm1 ln_bwd launch is gone).
+# CSU_FUSE_LN_QKV=0: the unfused launches (csu_gemm_ws + csu_layernorm_bwd), for A/B runs and tests.
+FUSE_LN_QKV = os.environ.get("CSU_FUSE_LN_QKV", "1") != "0"
 
 
 def ln_linear_ws(x: torch.Tensor, ln: torch.nn.LayerNorm, lin: torch.nn.Linear):

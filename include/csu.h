@@ -346,7 +346,8 @@ int csu_gemm_ws(long M, int N, int K, const void* x, int ldx, const void* w_frag
                 int out_dtype, void* out, void* stream);
 /* The input gradient of a LayerNorm -> Linear pair (CSWinBlock norm1 -> qkv, cswin:357 / 337) with the
  * LayerNorm backward in the GEMM's epilogue: dh = dy (M, K) @ W^T-fragments (wt_frag: the (C, K) weight
- * transpose, fragment-ordered) is never written; instead dx (M, C) fp32 = dres + rstd (g - mean(g) -
+ * transpose, fragment-ordered) is never written -- it is rounded to bf16 as csu_gemm_ws would store it
+ * and consumed in the kernel; instead dx (M, C) fp32 = dres + rstd (g - mean(g) -
  * xhat mean(g xhat)), g = dh * gamma, xhat = (x - mean) rstd, its bf16 copy dx_bf16, and the dgamma /
  * dbeta column partials of every 64-token block into part [M / 64][2C] (reduce them with
  * csu_layernorm_param_reduce_batch, nblocks = M / 64).  x fp32 (M, C); dres fp32 (M, C) or NULL.
