@@ -89,6 +89,16 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Power-of-two scale of an e4m3 row: the smallest 2^e with amax / 2^e <= 448 (1 for amax = 0), read off
+// the float's own exponent and mantissa (448 = 0.875 * 2^9).  exp2f(ceilf(log2f(amax / 448))) is not that:
+// for an amax one ulp above 448 * 2^k the fp32 logarithm rounds to k, and the scale 2^k leaves amax / s > 448.
+__device__ __forceinline__ float e4m3_row_scale(float amax) {
+    if (!(amax > 0.f)) return 1.f;
+    int e;
+    const float m = frexpf(amax, &e);   // amax = m 2^e, 0.5 <= m < 1
+    return ldexpf(1.f, max(e - (m <= 0.875f ? 9 : 8), -126));
+}
+
 // Row of the 32x32 MFMA accumulator register `reg` held by lane half `h` (C/D map, gfx950):
 // row = (reg & 3) + 8 * (reg >> 2) + 4 * h, column = lane & 31.
 __device__ __forceinline__ constexpr int crow(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }

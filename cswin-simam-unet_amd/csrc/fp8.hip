@@ -1,6 +1,7 @@
 // fp8-e4m3 weight quantization for the 1024x1024 configuration (BASELINE config 5: "fp8-e4m3
 // weights, bf16 activations, fp32 accumulate", SURVEY §8 d).  Each row (output feature) of a
-// Linear weight gets a power-of-two scale s = 2^ceil(log2(amax / 448)) (448 = e4m3fn max), so
+// Linear weight gets a power-of-two scale s = 2^ceil(log2(amax / 448)) (448 = e4m3fn max; computed exactly by
+// e4m3_row_scale in common.hpp -- an fp32 log2f rounds to the integer just above a boundary), so
 // every quantised value q * s is exactly representable in bf16 and the kernels that consume the
 // dequantised bf16 shadow compute on exactly the e4m3 weights.  Round-to-nearest-even, OCP
 // e4m3fn (v_cvt_pk_fp8_f32); |w / s| <= 448 by construction, so nothing saturates.
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(NT) void quant_e4m3_rows(const csu_fp8_item* __rest
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     // power-of-two scale: the smallest 2^e with amax / 2^e <= 448
-    const float s = amax > 0.f ? exp2f(ceilf(log2f(amax / 448.f))) : 1.f;
+    const float s = e4m3_row_scale(amax);
     const float inv = 1.f / s;   // exact (power of two)
     if (threadIdx.x == 0 && it.scales) it.scales[row] = s;
     for (int c = threadIdx.x; c < it.cols; c += NT) {
@@ -55,8 +56,6 @@ __global__ __launch_bounds__(NT) void quant_e4m3_rows(const csu_fp8_item* __rest
 // shadow), and through LDS tiles the transposed shadow and the fp8 fused Mlp's operand layouts
 // (q_perm: columns permuted within 64-groups; q_t: transposed; q_tp: transposed with permuted columns).
 constexpr int T8S = 68;   // byte row stride of the e4m3 transposition tile (4 column groups on distinct banks)
-
-__device__ __forceinline__ float row_scale_of(float amax) { return amax > 0.f ? exp2f(ceilf(log2f(amax / 448.f))) : 1.f; }
 
 __global__ __launch_bounds__(NT) void quant_e4m3_shadow(const csu_fp8_shadow_item* __restrict__ items, int count) {
     __shared__ __attribute__((aligned(16))) bf16 T[64][64 + 8];
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(NT) void quant_e4m3_shadow(const csu_fp8_shadow_ite
     }
     amax = fmaxf(amax, __shfl_xor(amax, 1));
     amax = fmaxf(amax, __shfl_xor(amax, 2));
-    const float sc = row_scale_of(amax);
+    const float sc = e4m3_row_scale(amax);
     if (rok && (threadIdx.x & 3) == 0 && it.scales) it.scales[row] = sc;
     const float inv = 1.f / sc;   // exact: a power of two
     bf16* const sh = (bf16*)it.shadow;

@@ -113,14 +113,14 @@ __global__ __launch_bounds__(NT) void ln_fwd(int rows, int C, float eps, const T
         const unsigned ro = (lane % LPR == 0 && row < rows) ? (unsigned)row * 4u : kOOB;
         if constexpr (sizeof(TY) == 1) {
             // fp8 output (the e4m3 GEMM's activation operand, csrc/fp8gemm.hip): the row's amax over
-            // its LPR lanes, power-of-two scale s = 2^ceil(log2(amax / 448)) as the weights'
+            // its LPR lanes, power-of-two scale s = 2^ceil(log2(amax / 448)) as the weights' (exact: e4m3_row_scale)
             // (csrc/fp8.hip), y / s rounded to e4m3 (RNE; |y / s| <= 448, nothing saturates)
             float am = 0.f;
 #pragma unroll
             for (int j = 0; j < V; ++j) am = fmaxf(am, fabsf(o[j]));
 #pragma unroll
             for (int m = LPR / 2; m > 0; m >>= 1) am = fmaxf(am, __shfl_xor(am, m, 64));
-            const float s = am > 0.f ? exp2f(ceilf(log2f(am / 448.f))) : 1.f;
+            const float s = e4m3_row_scale(am);
             const float inv = 1.f / s;
             unsigned w[V / 4];
 #pragma unroll

@@ -413,7 +413,9 @@ typedef struct {
 int csu_cast_bf16_batch(const csu_cast_item* items, int count, long total_tiles, void* stream);
 
 /* fp8-e4m3 weights (BASELINE config 5): per item (rows x cols fp32 row-major, row = output feature),
- * per row the power-of-two scale s = 2^ceil(log2(amax/448)), q = e4m3fn(w / s) (RNE), and
+ * per row the power-of-two scale s = 2^ceil(log2(amax/448)) -- the smallest power of two with amax / s <= 448,
+ * taken exactly from the float's exponent and mantissa (e4m3_row_scale, csrc/common.hpp), never through an fp32
+ * log2 --, q = e4m3fn(w / s) (RNE), and
  * dst = q * s in fp32 (exact in bf16: the cast cache then makes the kernels' bf16 shadows from it);
  * dst_q (optional) the e4m3 bytes, scales (optional) s per row.  items: DEVICE array sorted by
  * row0 (prefix sum of rows); one block per row of every item. */
@@ -452,7 +454,8 @@ int csu_quant_e4m3_shadow_batch(const csu_fp8_shadow_item* items, int count, lon
 int csu_fp8_gemm(long M, int N, int K, const void* aq, const float* sa, const void* wq, const float* sw,
                  const float* bias, void* out, void* stream);
 /* LayerNorm forward with an e4m3 output: yq = e4m3fn(LN(x) / s) (RNE), yscale[row] = s =
- * 2^ceil(log2(amax_row / 448)) (1 for an all-zero row); mean / rstd as csu_layernorm_fwd. */
+ * 2^ceil(log2(amax_row / 448)) (1 for an all-zero row; exact, as the weights': e4m3_row_scale); mean / rstd as
+ * csu_layernorm_fwd. */
 int csu_layernorm_fwd_fp8(int rows, int C, float eps, int xdtype, const void* x, const float* gamma,
                           const float* beta, void* yq, float* yscale, float* mean, float* rstd, void* stream);
 /* the same, also writing ydq (bf16, rows x C, or NULL) = e4m3fn(yq) * yscale[row] exactly: the
