@@ -15,6 +15,11 @@
 // the device coefficient ctl[1] that csu_grad_norm_finish wrote (grad_norm.hip) while the element is
 // in registers -- no extra traffic -- and may skip the whole step when ctl[2] says the gradient
 // norm was not finite.
+//
+// Weight EMA (csu_adamw_step_ema): the EMA instantiations also update an exponential moving average
+// of every parameter from the updated value in registers -- + 8 B per parameter (read and write the
+// EMA value), no extra launch, against 12 B for a separate pass (ema.hip, the stand-alone form the
+// fused one matches bit for bit).
 #include "adamw_items.hpp"
 
 namespace csu {
@@ -50,108 +55,85 @@ __device__ __forceinline__ void adam4(const AdamConst& k, float* pv, const float
     }
 }
 
-template <bool L2, bool CLIP>
-__device__ __forceinline__ void update(const AdamConst& k, float* p, const float* g, float* m, float* v, long i, int n,
-                                       bool vec, float* pv) {
-    float gv[4], mv[4], vv[4];
+// ev: EMA only, the four EMA values (loaded beside the others, stored with the same 16-B stores); e == null:
+// no EMA for this item
+template <bool L2, bool CLIP, bool EMA>
+__device__ __forceinline__ void update(const AdamConst& k, float* p, const float* g, float* m, float* v, float* e, float ew,
+                                       long i, int n, bool vec, float* pv) {
+    float gv[4], mv[4], vv[4], ev[4];
     ld4n(p, i, n, vec, pv);
     ld4n(g, i, n, vec, gv);
     ld4n(m, i, n, vec, mv);
     ld4n(v, i, n, vec, vv);
+    if constexpr (EMA) {
+        if (e) ld4n(e, i, n, vec, ev);
+    }
     adam4<L2, CLIP>(k, pv, gv, mv, vv);
     st4n(p, i, n, vec, pv);
     st4n(m, i, n, vec, mv);
     st4n(v, i, n, vec, vv);
+    if constexpr (EMA) {
+        if (e) {   // while pv holds the updated parameter: + one read and one write of the EMA value
+            ema4(ew, pv, ev);
+            st4n(e, i, n, vec, ev);
+        }
+    }
 }
 
 // L2 = false: AdamW (decoupled decay, cswin:937-941); L2 = true: Adam with L2 weight decay, the
 // plain UNet's optim.Adam(weight_decay) (unet:486-490): g += wd * param before the moments.
 // Shadow modes (csu.h): tile items update a 64 x 64 tile and write W and, through LDS, W^T in
 // bf16; flat items write the bf16 copy at the same index, conv items scatter the OHWI / IHWO
-// layouts (the csu_cast_bf16_batch layouts, now made from the updated fp32 value in registers).
+// layouts (the csu_cast_bf16_batch layouts, now made from the updated fp32 value in registers;
+// walk_chunk, adamw_items.hpp).
 // CLIP (csu_adamw_step_ex): ctl = the device scalars of csu_grad_norm_finish; g <- g * ctl[1] before
 // anything else (the L2 term included), and with skip != 0 and ctl[2] == 0 (non-finite gradient
 // norm) every workgroup returns before it loads or stores anything else.  ctl and skip are unused
 // without CLIP.
-template <bool L2, bool CLIP = false>
+// EMA (csu_adamw_step_ema): ema[item] <- ema + w (param - ema) from the updated parameter, w = 1 - d
+// once per workgroup (ema_weight); a skipped step leaves the EMA alone.  The ema_* arguments are
+// unused without EMA.
+template <bool L2, bool CLIP = false, bool EMA = false>
 __global__ __launch_bounds__(NT) void adamw_kernel(const csu_adamw_item* __restrict__ items, int count, const float* lr_dev,
                                                    float lr_host, float beta1, float beta2, float eps, float wd,
-                                                   const float* step_dev, float step_host, const float* ctl, int skip) {
-    __shared__ bf16 tile[64][64 + 2];
+                                                   const float* step_dev, float step_host, const float* ctl, int skip,
+                                                   float* const* __restrict__ ema, const float* ema_n_dev, float ema_decay,
+                                                   int ema_warmup) {
+    __shared__ ShadowTile tile;
     if constexpr (CLIP) {
         if (skip && ctl[2] == 0.f) return;
     }
     const long b = blockIdx.x;
-    const csu_adamw_item it = items[find_item(items, count, b)];
+    const int idx = find_item(items, count, b);
+    const csu_adamw_item it = items[idx];
     const float lr = lr_dev ? *lr_dev : lr_host;
     const float step = step_dev ? *step_dev : step_host;
     float coef = 1.f;
     if constexpr (CLIP) coef = ctl[1];   // read beside lr / step: its latency hides behind theirs
+    float* e = nullptr;
+    float ew = 0.f;
+    if constexpr (EMA) {
+        e = ema[idx];
+        ew = ema_weight(ema_n_dev, ema_decay, ema_warmup);
+    }
     const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
     const AdamConst k{beta1, beta2, eps, wd, lr / bc1, sqrtf(bc2), L2 ? 1.f : 1.f - lr * wd, coef};
     float* p = it.param;
     const float* g = it.grad;
     float* m = it.exp_avg;
     float* v = it.exp_avg_sq;
-    bf16* sh = (bf16*)it.shadow;
-    bf16* sht = (bf16*)it.shadow_t;
-    if (is_tiled(it)) {   // 64 x 64 tile of a rows x cols matrix: W and W^T shadows
-        const int tk = (it.cols + 63) / 64;
-        const long t = b - it.chunk0;
-        const int r0 = (int)(t / tk) * 64, c0 = (int)(t % tk) * 64;
-        const int cq = (threadIdx.x & 15) * 4, rr = threadIdx.x >> 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r0 + rr + 16 * i, c = c0 + cq;
-            float pv[4] = {0.f, 0.f, 0.f, 0.f};
-            if (r < it.rows && c < it.cols) {
-                const int n = min(4, it.cols - c);
-                const bool vec = (it.cols & 3) == 0;   // then n == 4 and the row segment is 16-B aligned
-                const long e = (long)r * it.cols + c;
-                update<L2, CLIP>(k, p, g, m, v, e, n, vec, pv);
-                st4n(sh, e, n, vec, pv);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) tile[rr + 16 * i][cq + j] = (bf16)pv[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {   // W^T rows c0.. (cols rows): thread -> (column c, 4 rows)
-            const int c = c0 + rr + 16 * i;
-            if (c >= it.cols) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = r0 + cq + j;
-                if (r < it.rows) sht[(long)c * it.rows + r] = tile[cq + j][rr + 16 * i];
-            }
-        }
-        return;
-    }
-    const long base = (b - it.chunk0) * CH;
-    const bool vec = (it.numel & 3) == 0;
-#pragma unroll
-    for (int q = 0; q < PER / 4; ++q) {
-        const long i = base + ((long)q * NT + threadIdx.x) * 4;   // 4 consecutive elements, coalesced per q
-        if (i >= it.numel) break;
-        const int n = vec ? 4 : (int)(it.numel - i < 4 ? it.numel - i : 4);
-        float pv[4];
-        update<L2, CLIP>(k, p, g, m, v, i, n, vec, pv);
-        if (!sh) continue;
-        if (it.taps > 0) {   // conv weight [n][c][tap] -> OHWI [n][tap][c] (stride cols_pad), IHWO [c][tap][n]
-            const unsigned TP = it.taps, CT = (unsigned)it.cols * TP;
-            const unsigned CP = it.cols_pad > it.cols ? it.cols_pad : it.cols;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j >= n) break;
-                const unsigned e = (unsigned)(i + j), o = e / CT, rem = e - o * CT, c = rem / TP, t = rem - c * TP;
-                const bf16 w = (bf16)pv[j];
-                sh[(o * TP + t) * CP + c] = w;
-                if (sht) sht[(c * TP + t) * (unsigned)it.rows + o] = w;
-            }
-        } else {
-            st4n(sh, i, n, vec, pv);
-        }
-    }
+    walk_chunk<true>(it, b, &tile, [&](long i, int n, bool vec, float* pv) {
+        update<L2, CLIP, EMA>(k, p, g, m, v, e, ew, i, n, vec, pv);
+    });
+}
+
+template <bool L2, bool CLIP, bool EMA>
+void launch_adamw(const csu_adamw_item* items, int count, long total_chunks, const float* lr_dev, float lr, float beta1,
+                  float beta2, float eps, float wd, const float* step_dev, float step, const float* ctl, int skip,
+                  float* const* ema, const float* ema_n_dev, float ema_decay, int ema_warmup, hipStream_t st) {
+    adamw_kernel<L2, CLIP, EMA><<<(unsigned)total_chunks, NT, 0, st>>>(items, count, lr_dev, lr, beta1, beta2, eps, wd,
+                                                                       step_dev, step, ctl, skip, ema, ema_n_dev, ema_decay,
+                                                                       ema_warmup);
 }
 
 }  // namespace
@@ -165,8 +147,8 @@ extern "C" int csu_adamw_step(const csu_adamw_item* items, int count, long total
                               float beta1, float beta2, float eps, float weight_decay, const float* step_dev, float step,
                               void* stream) {
     if (!items || count < 1 || total_chunks < 1) return fail(CSU_E_ARG, "adamw: empty item table");
-    adamw_kernel<false><<<(unsigned)total_chunks, NT, 0, as_stream(stream)>>>(items, count, lr_dev, lr, beta1, beta2, eps,
-                                                                              weight_decay, step_dev, step, nullptr, 0);
+    launch_adamw<false, false, false>(items, count, total_chunks, lr_dev, lr, beta1, beta2, eps, weight_decay, step_dev,
+                                      step, nullptr, 0, nullptr, nullptr, 0.f, 0, as_stream(stream));
     return check_launch("adamw");
 }
 
@@ -174,8 +156,8 @@ extern "C" int csu_adam_l2_step(const csu_adamw_item* items, int count, long tot
                                 float beta1, float beta2, float eps, float weight_decay, const float* step_dev, float step,
                                 void* stream) {
     if (!items || count < 1 || total_chunks < 1) return fail(CSU_E_ARG, "adam_l2: empty item table");
-    adamw_kernel<true><<<(unsigned)total_chunks, NT, 0, as_stream(stream)>>>(items, count, lr_dev, lr, beta1, beta2, eps,
-                                                                             weight_decay, step_dev, step, nullptr, 0);
+    launch_adamw<true, false, false>(items, count, total_chunks, lr_dev, lr, beta1, beta2, eps, weight_decay, step_dev,
+                                     step, nullptr, 0, nullptr, nullptr, 0.f, 0, as_stream(stream));
     return check_launch("adam_l2");
 }
 
@@ -186,10 +168,33 @@ extern "C" int csu_adamw_step_ex(const csu_adamw_item* items, int count, long to
     if (!ctl) return fail(CSU_E_ARG, "adamw_step_ex: null ctl (csu_grad_norm_finish writes it)");
     hipStream_t st = as_stream(stream);
     if (l2)
-        adamw_kernel<true, true><<<(unsigned)total_chunks, NT, 0, st>>>(items, count, lr_dev, lr, beta1, beta2, eps,
-                                                                        weight_decay, step_dev, step, ctl, skip_nonfinite);
+        launch_adamw<true, true, false>(items, count, total_chunks, lr_dev, lr, beta1, beta2, eps, weight_decay, step_dev,
+                                        step, ctl, skip_nonfinite, nullptr, nullptr, 0.f, 0, st);
     else
-        adamw_kernel<false, true><<<(unsigned)total_chunks, NT, 0, st>>>(items, count, lr_dev, lr, beta1, beta2, eps,
-                                                                         weight_decay, step_dev, step, ctl, skip_nonfinite);
+        launch_adamw<false, true, false>(items, count, total_chunks, lr_dev, lr, beta1, beta2, eps, weight_decay, step_dev,
+                                         step, ctl, skip_nonfinite, nullptr, nullptr, 0.f, 0, st);
     return check_launch("adamw_step_ex");
+}
+
+extern "C" int csu_adamw_step_ema(const csu_adamw_item* items, int count, long total_chunks, const float* lr_dev, float lr,
+                                  float beta1, float beta2, float eps, float weight_decay, const float* step_dev, float step,
+                                  const float* ctl, int skip_nonfinite, int l2, float* const* ema,
+                                  const float* ema_updates_dev, float ema_decay, int ema_warmup, void* stream) {
+    if (!items || count < 1 || total_chunks < 1) return fail(CSU_E_ARG, "adamw_step_ema: empty item table");
+    if (!ema) return fail(CSU_E_ARG, "adamw_step_ema: null EMA pointer array");
+    if (ema_warmup && !ema_updates_dev) return fail(CSU_E_ARG, "adamw_step_ema: warmup needs the device update count");
+    if (!(ema_decay >= 0.f && ema_decay <= 1.f)) return fail(CSU_E_ARG, "adamw_step_ema: decay outside [0, 1]");
+    hipStream_t st = as_stream(stream);
+    auto go = [&](auto fn) {
+        fn(items, count, total_chunks, lr_dev, lr, beta1, beta2, eps, weight_decay, step_dev, step, ctl, skip_nonfinite,
+           ema, ema_updates_dev, ema_decay, ema_warmup, st);
+    };
+    if (ctl) {   // null ctl: no clipping
+        if (l2) go(launch_adamw<true, true, true>);
+        else go(launch_adamw<false, true, true>);
+    } else {
+        if (l2) go(launch_adamw<true, false, true>);
+        else go(launch_adamw<false, false, true>);
+    }
+    return check_launch("adamw_step_ema");
 }

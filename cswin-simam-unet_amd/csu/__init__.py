@@ -14,6 +14,7 @@ from .train import (bce_loss, dice_coefficient, evaluate_model, iou_score, make_
 from .losses import (MultiClassSegLoss, SegLoss, bce_dice_loss, ce_dice_loss, ce_loss, dice_loss, multiclass_dice_loss,
                      tversky_loss)
 from .optim import FusedAdam, FusedAdamW
+from .ema import WeightEMA
 from . import rng
 from .rng import manual_seed
 
@@ -21,4 +22,4 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "img2windows", "windows2img", "SimAM", "simam", "bce_loss", "dice_coefficient", "evaluate_model",
            "iou_score", "make_optimizer", "make_scheduler", "train_model", "train_step", "FusedAdamW", "FusedAdam",
            "rng", "manual_seed", "SegLoss", "dice_loss", "bce_dice_loss", "tversky_loss",
-           "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss"]
+           "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss", "WeightEMA"]

@@ -146,6 +146,12 @@ _SIGS = {
     "csu_adamw_step_ex": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_float, c_float, c_float,
                                          c_float, c_float, c_void_p, c_float, c_void_p, ctypes.c_int, ctypes.c_int,
                                          c_void_p]),
+    "csu_adamw_step_ema": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_float, c_float, c_float,
+                                          c_float, c_float, c_void_p, c_float, c_void_p, ctypes.c_int, ctypes.c_int,
+                                          c_void_p, c_void_p, c_float, ctypes.c_int, c_void_p]),
+    "csu_ema_update": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_long, c_void_p, c_float, ctypes.c_int,
+                                      c_void_p]),
+    "csu_ema_swap": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_long, c_void_p]),
     "csu_gemm_ex": (ctypes.c_int, [ctypes.POINTER(GemmDesc), c_void_p]),
     "csu_mlp_fwd_ln": (ctypes.c_int, [ctypes.c_long, ctypes.c_int] + [c_void_p] * 8 + [c_void_p, c_void_p, c_float, c_void_p,
                                                                                c_void_p, c_void_p, c_void_p]),

@@ -17,7 +17,11 @@ and the step kernel multiplies every gradient element by the resulting coefficie
 it in registers (csu_adamw_step_ex) -- ``torch.nn.utils.clip_grad_norm_`` + ``step()`` without a
 host sync, so it is captured with the step.  ``p.grad`` itself is left UNSCALED by this fused path
 (only the update sees the clipped value); ``csu.optim.clip_grad_norm_`` is the stand-alone,
-in-place form for other optimizers."""
+in-place form for other optimizers.
+
+Weight EMA (``ema=``, a csu.ema.WeightEMA): the same launch also updates the exponential moving
+average of every parameter it steps (csu_adamw_step_ema), from the updated value in registers -- 8 B
+per parameter more, no launch after the step, captured with it."""
 from __future__ import annotations
 
 import numpy as np
@@ -31,6 +35,7 @@ _ITEM = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_a
                   ("chunk0", "<i8"), ("shadow", "<u8"), ("shadow_t", "<u8"), ("rows", "<i4"), ("cols", "<i4"),
                   ("taps", "<i4"), ("cols_pad", "<i4")])
 _NO_SHADOW = (0, 0, 0, 0, 0, 0)
+_TABLE_REC = _ITEM.itemsize + 8     # bytes reserved per parameter: its item + its EMA pointer
 
 
 def _chunks(n, spec, chunk):
@@ -46,12 +51,16 @@ class FusedAdamW(torch.optim.Optimizer):
     _L2 = False   # FusedAdam: coupled L2 weight decay (torch.optim.Adam)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema=None):
         """``max_grad_norm``: clip the global L2 norm of all gradients (all param groups together, as
         ``clip_grad_norm_(model.parameters(), max_grad_norm)``) before the update; ``skip_nonfinite``:
         a step whose gradient norm is inf / NaN changes nothing (parameters, moments, shadows and
         the step count keep their values; ``skipped_steps`` counts it).  Both are plain attributes,
-        not param-group entries: state_dict() keeps torch.optim.AdamW's format."""
+        not param-group entries: state_dict() keeps torch.optim.AdamW's format.
+        ``ema``: a csu.ema.WeightEMA of the model these parameters belong to; step() then updates it in
+        the same launch (csu_adamw_step_ema), from every updated parameter while it is in registers.
+        A parameter without a gradient is not stepped and its average stays as it is; a skipped
+        non-finite step leaves the averages and their update count alone."""
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay:
             raise ValueError("invalid AdamW hyper-parameter")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
@@ -61,6 +70,7 @@ class FusedAdamW(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable))
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema = ema
         # device scalars of the norm pass, allocated HERE, outside any capture (see _capture_dev below):
         # _ctl = (norm, clip coefficient, finite flag, 0) written by csu_grad_norm_finish
         dev0 = next((p.device for g in self.param_groups for p in g["params"] if p.is_cuda), None)
@@ -76,14 +86,16 @@ class FusedAdamW(torch.optim.Optimizer):
         self._gstate = {}
         self._deferred = []
         self._captured = []
-        # one pinned table buffer per group, reserved for a HIP-graph capture of step()
-        self._pinned = {gi: torch.empty(max(1, len(g["params"])) * _ITEM.itemsize, dtype=torch.uint8, pin_memory=True)
+        # one pinned table buffer per group, reserved for a HIP-graph capture of step(): the items and,
+        # behind them, the parallel EMA pointer array (8 B per item; built, cached, frozen and copied
+        # with the table under the same key)
+        self._pinned = {gi: torch.empty(max(1, len(g["params"])) * _TABLE_REC, dtype=torch.uint8, pin_memory=True)
                         for gi, g in enumerate(self.param_groups)} if torch.cuda.is_available() else {}
         # ... and its device image, allocated HERE, outside any capture: a buffer allocated inside the
         # capture comes from the graph's private pool, where it may alias memory an earlier captured
         # kernel writes on every replay -- fine for buffers the graph itself fills, fatal for one
         # filled once after the capture (finish_capture)
-        self._capture_dev = {gi: torch.empty(max(1, len(g["params"])) * _ITEM.itemsize, dtype=torch.uint8,
+        self._capture_dev = {gi: torch.empty(max(1, len(g["params"])) * _TABLE_REC, dtype=torch.uint8,
                                              device=g["params"][0].device)
                              for gi, g in enumerate(self.param_groups) if g["params"] and g["params"][0].is_cuda}
 
@@ -94,7 +106,7 @@ class FusedAdamW(torch.optim.Optimizer):
         graphs captured before keep their own tables."""
         for gi, g in enumerate(self.param_groups):
             if g["params"] and g["params"][0].is_cuda and (gi not in self._pinned or gi not in self._capture_dev):
-                n = max(1, len(g["params"])) * _ITEM.itemsize
+                n = max(1, len(g["params"])) * _TABLE_REC
                 self._pinned[gi] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
                 self._capture_dev[gi] = torch.empty(n, dtype=torch.uint8, device=g["params"][0].device)
         if self._ctl is not None and self._clipping():
@@ -148,7 +160,7 @@ class FusedAdamW(torch.optim.Optimizer):
                                                            self._ctl.data_ptr(), stream_ptr(dev)),
                0, 0, prec="f32")
 
-    def _table(self, gi, items, device):
+    def _table(self, gi, items, device, ema=None):
         """Device item table for the current (param, grad) buffers, rebuilt when they change
         (e.g. every step under zero_grad(set_to_none=True) when the allocator hands out other grad
         buffers).  Eager: an asynchronous copy from a fresh pinned buffer (no host sync; the
@@ -156,8 +168,11 @@ class FusedAdamW(torch.optim.Optimizer):
         the host image goes to a pinned buffer reserved for that capture (pinned memory cannot be
         allocated while capturing) and is copied ONCE after the capture (finish_capture) into a
         device buffer allocated outside the graph's memory pool and kept for the optimizer's
-        lifetime -- no copy node in the replayed graph."""
-        key = (gi,) + tuple(v for it in items for v in it[:4] + it[5])
+        lifetime -- no copy node in the replayed graph.
+        ``ema``: the EMA tensor address of every item (0: none), laid out as a uint64 array behind the
+        items in the same buffers -- the ``float* const* ema`` of csu_adamw_step_ema, at byte offset
+        len(items) * sizeof(csu_adamw_item)."""
+        key = (gi,) + tuple(v for it in items for v in it[:4] + it[5]) + (tuple(ema) if ema is not None else ())
         t = self._tables.get(gi)
         if t is not None and t[0] == key:
             return t
@@ -167,7 +182,8 @@ class FusedAdamW(torch.optim.Optimizer):
         for i, (p, g, m, v, n, spec) in enumerate(items):
             rec[i] = (p, g, m, v, n, c0) + tuple(spec)
             c0 += _chunks(n, spec, chunk)
-        raw = np.frombuffer(rec.tobytes(), dtype=np.uint8)
+        tail = np.array(ema, dtype="<u8").tobytes() if ema is not None else b""
+        raw = np.frombuffer(rec.tobytes() + tail, dtype=np.uint8)
         if torch.cuda.is_current_stream_capturing():
             host = self._pinned.get(gi)
             dev = self._capture_dev.get(gi)
@@ -200,9 +216,12 @@ class FusedAdamW(torch.optim.Optimizer):
                 loss = closure()
         from .ops import shadow_spec, shadows_written
         clip = self._clipping()
+        ema = self.ema
+        if ema is not None and ema.swapped:
+            raise RuntimeError("FusedAdamW.step() while the EMA weights are swapped in (inside WeightEMA.applied())")
         work = []
         for gi, group in enumerate(self.param_groups):
-            items, dev, keep, shadowed = [], None, [], []
+            items, dev, keep, shadowed, eptr, enumel = [], None, [], [], [], 0
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -225,16 +244,27 @@ class FusedAdamW(torch.optim.Optimizer):
                 items.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                               p.numel(), spec or _NO_SHADOW))
                 dev = p.device
+                if ema is not None:
+                    e = ema.tensor_for(p)
+                    eptr.append(0 if e is None else e.data_ptr())
+                    enumel += 0 if e is None else p.numel()
             if not items:
                 continue
-            work.append({"gi": gi, "group": group, "items": items, "dev": dev, "keep": keep, "shadowed": shadowed})
+            work.append({"gi": gi, "group": group, "items": items, "dev": dev, "keep": keep, "shadowed": shadowed,
+                         "ema": eptr if ema is not None else None, "ema_numel": enumel})
         if clip and work:
             # one norm over all param groups, ordered before the step-count adds and the step kernels
             for w in work:
-                w["table"] = self._table(w["gi"], w["items"], w["dev"])
+                w["table"] = self._table(w["gi"], w["items"], w["dev"], w["ema"])
             self._norm_pass(work)
             if self.skip_nonfinite:
                 self.skipped_steps += self._ctl[2] == 0
+        if ema is not None and work:
+            # one EMA update per step() whatever the number of groups; a skipped step does not count
+            if clip and self.skip_nonfinite:
+                ema.num_updates += self._ctl[2]
+            else:
+                ema.num_updates += 1
         for w in work:
             gi, group, items, dev, shadowed = w["gi"], w["group"], w["items"], w["dev"], w["shadowed"]
             gs = self._gstate.get(gi)
@@ -253,19 +283,27 @@ class FusedAdamW(torch.optim.Optimizer):
             for p in group["params"]:
                 if p.grad is not None:
                     self.state[p]["step"] = gs["step"]
-            _, _, table, n, chunks = self._table(gi, items, dev)
+            _, _, table, n, chunks = self._table(gi, items, dev, w["ema"])
             lr_ptr = gs["lr"].data_ptr() if group["capturable"] else None
             b1, b2 = group["betas"]
             numel = sum(it[4] for it in items)
             args = (table.data_ptr(), n, chunks, lr_ptr, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                     float(group["weight_decay"]), gs["step"].data_ptr(), 0.0)
-            if clip:
+            nema = 0
+            if ema is not None:
+                fn = lib().csu_adamw_step_ema
+                args += (self._ctl.data_ptr() if clip else None, int(self.skip_nonfinite), int(self._L2),
+                         table.data_ptr() + n * _ITEM.itemsize, ema.num_updates.data_ptr(), float(ema.decay),
+                         int(ema.warmup))
+                nema = 8 * w["ema_numel"]       # algorithmic: the EMA value read and written once
+            elif clip:
                 fn = lib().csu_adamw_step_ex
                 args += (self._ctl.data_ptr(), int(self.skip_nonfinite), int(self._L2))
             else:
                 fn = lib().csu_adam_l2_step if self._L2 else lib().csu_adamw_step
             nsh = sum(2 * it[4] * (1 + (it[5][1] != 0)) for it in items if it[5][0])
-            launch("adamw", lambda: fn(*args, stream_ptr(dev)), 12 * numel, 28 * numel + nsh, idem=False, prec="f32")
+            launch("adamw", lambda: fn(*args, stream_ptr(dev)), 12 * numel, 28 * numel + nsh + nema, idem=False,
+                   prec="f32")
             # (a skipped step leaves the shadows as they are: still the bf16 image of the unchanged weights)
             shadows_written(shadowed)
         return loss
@@ -338,9 +376,9 @@ class FusedAdam(FusedAdamW):
     _L2 = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema=ema)
 
 
 def _grads_of(parameters):

@@ -90,9 +90,10 @@ def save_model(model, path: str = "cswinunet_segmentation_model.pth") -> Optiona
 
 
 def save_checkpoint(path: str, model, optimizer=None, scheduler=None, epoch: int = 0,
-                    history: Optional[Dict[str, List[float]]] = None) -> Optional[str]:
+                    history: Optional[Dict[str, List[float]]] = None, ema=None) -> Optional[str]:
     """Everything train_model needs to continue: model / optimizer / scheduler state, the number of
-    finished epochs and the history so far.  Written atomically (tmp file + rename)."""
+    finished epochs and the history so far.  Written atomically (tmp file + rename).  ``ema``: a
+    csu.ema.WeightEMA, saved as the ``"ema"`` entry (its state_dict: tensors, numbers and booleans)."""
     if not _rank0():
         return None
     ck = {"model": _unwrap(model).state_dict(), "epoch": int(epoch),
@@ -101,16 +102,19 @@ def save_checkpoint(path: str, model, optimizer=None, scheduler=None, epoch: int
         ck["optimizer"] = optimizer.state_dict()
     if scheduler is not None:
         ck["scheduler"] = scheduler.state_dict()
+    if ema is not None:
+        ck["ema"] = ema.state_dict()
     tmp = path + ".tmp"
     torch.save(ck, tmp)
     os.replace(tmp, path)
     return path
 
 
-def load_checkpoint(path: str, model, optimizer=None, scheduler=None, map_location=None):
+def load_checkpoint(path: str, model, optimizer=None, scheduler=None, map_location=None, ema=None):
     """Restore a save_checkpoint file into the given objects (weights_only load: nothing in the file
     is executed).  Returns (epochs finished, history).  A FusedAdamW with a device lr picks up the
-    restored lr through sync_lr()."""
+    restored lr through sync_lr().  ``ema``: a csu.ema.WeightEMA restored from the file's ``"ema"`` entry
+    (a file without one leaves it as it is)."""
     ck = torch.load(path, map_location=map_location, weights_only=True)
     _unwrap(model).load_state_dict(ck["model"])
     if optimizer is not None and "optimizer" in ck:
@@ -119,4 +123,6 @@ def load_checkpoint(path: str, model, optimizer=None, scheduler=None, map_locati
             optimizer.sync_lr()
     if scheduler is not None and "scheduler" in ck:
         scheduler.load_state_dict(ck["scheduler"])
+    if ema is not None and "ema" in ck:
+        ema.load_state_dict(ck["ema"])
     return int(ck.get("epoch", 0)), {k: list(v) for k, v in ck.get("history", {}).items()}

@@ -165,9 +165,11 @@ def _graph_cache(model):
 
 
 def _drop_stale_train_graphs(cache, optimizer, reducer):
-    """A new optimizer or reducer for the model: the train graphs captured for the old ones (and the
-    memory pools they hold) are released."""
-    for k in [k for k in cache if k[0] == "train" and (k[-2], k[-1]) != (id(optimizer), id(reducer))]:
+    """A new optimizer or reducer for the model, or another EMA on the optimizer (the captured step
+    launch holds the EMA's pointers): the train graphs captured for the old ones (and the memory
+    pools they hold) are released."""
+    now = (id(getattr(optimizer, "ema", None)), id(optimizer), id(reducer))
+    for k in [k for k in cache if k[0] == "train" and k[-3:] != now]:
         del cache[k]
 
 
@@ -309,6 +311,7 @@ def train_step(model, images, masks, criterion, optimizer, reducer=None, amp_dty
         reducer.finish()
     _clip_for(optimizer)
     optimizer.step()
+    _ema_for(optimizer)
     with torch.no_grad():
         if st is not None:
             return torch.cat([loss.detach().double().view(1), st.double().reshape(-1)])
@@ -327,6 +330,16 @@ def _clip_for(optimizer):
         return
     params = [p for g in optimizer.param_groups for p in g["params"]]
     optimizer.grad_norm = torch.nn.utils.clip_grad_norm_(params, c)
+
+
+def _ema_for(optimizer):
+    """The weight EMA of an optimizer that carries one as ``optimizer.ema`` but does not update it
+    itself (make_optimizer's torch.optim.AdamW on the CPU): the stand-alone update after its step.
+    csu's FusedAdamW updates its EMA inside step()."""
+    from .optim import FusedAdamW
+    ema = getattr(optimizer, "ema", None)
+    if ema is not None and not isinstance(optimizer, FusedAdamW):
+        ema.update()
 
 
 def _clip_epoch(norms, optimizer, skipped0):
@@ -383,7 +396,8 @@ class _GraphedTrain:
 
 def train_model(model, train_loader, test_loader, criterion, optimizer, scheduler, device, num_epochs=100,
                 verbose: bool = True, checkpoint_path: Optional[str] = None,
-                resume_from: Optional[str] = None, amp_dtype=None, graph=None, reducer=None) -> Dict[str, List[float]]:
+                resume_from: Optional[str] = None, amp_dtype=None, graph=None, reducer=None,
+                ema=None) -> Dict[str, List[float]]:
     """Epoch loop with per-epoch history and ReduceLROnPlateau on the test loss (cswin:751-841).
 
     Beyond the reference: ``checkpoint_path`` writes a resumable checkpoint (model, optimizer,
@@ -401,20 +415,34 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     device scalars read once per epoch; without the options the history has the reference's keys.
     Multi-class (integer label maps): ``train_dice`` / ``train_iou`` / ``test_dice`` / ``test_iou`` are the
     macro means over the classes that occur, and four more keys, ``train_class_dice``, ``train_class_iou``,
-    ``test_class_dice`` and ``test_class_iou``, hold a list of K per-class values per epoch."""
+    ``test_class_dice`` and ``test_class_iou``, hold a list of K per-class values per epoch.
+    Weight EMA: ``ema`` (default: ``optimizer.ema``, which make_optimizer(ema_decay=...) sets; one passed
+    here to an optimizer without one is set as its ``ema``; the optimizer or train_step updates it every
+    step) is also evaluated every epoch, in place under
+    ``ema.applied()`` through the same evaluate_model (and the same cached eval graph), which adds
+    ``ema_test_loss``, ``ema_test_dice`` and ``ema_test_iou`` (multi-class: also ``ema_test_class_dice`` and
+    ``ema_test_class_iou``); the scheduler keeps stepping on the raw ``test_loss``, and checkpoints
+    carry the EMA.  Without an EMA the history has exactly the keys above."""
     history = {"train_loss": [], "train_dice": [], "train_iou": [], "test_loss": [], "test_dice": [], "test_iou": [],
                "learning_rates": []}
     clips = _clips(optimizer)
     if clips:
         history["grad_norm"], history["skipped_steps"] = [], []
+    if ema is None:
+        ema = getattr(optimizer, "ema", None)
+    elif getattr(optimizer, "ema", None) is None:
+        optimizer.ema = ema      # an EMA passed here alone: the optimizer (FusedAdamW) or train_step updates it
+    if ema is not None:
+        history["ema_test_loss"], history["ema_test_dice"], history["ema_test_iou"] = [], [], []
     rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
     start = 0
     if resume_from is not None:
         from .report import load_checkpoint
-        start, past = load_checkpoint(resume_from, model, optimizer, scheduler, map_location=device)
+        start, past = load_checkpoint(resume_from, model, optimizer, scheduler, map_location=device, ema=ema)
         for k in history:
             history[k] = list(past.get(k, []))
-        for k in ("train_class_dice", "train_class_iou", "test_class_dice", "test_class_iou"):
+        for k in ("train_class_dice", "train_class_iou", "test_class_dice", "test_class_iou", "ema_test_class_dice",
+                  "ema_test_class_iou"):
             if k in past:
                 history[k] = list(past[k])
     use_graph = graph is not False and _graphable(model, optimizer, device, criterion)
@@ -438,8 +466,8 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
             images = images.to(device, non_blocking=True)
             masks = masks.to(device, non_blocking=True)
             if use_graph:
-                key = ("train", tuple(images.shape), tuple(masks.shape), amp_dtype, criterion, id(optimizer),
-                       id(reducer))
+                key = ("train", tuple(images.shape), tuple(masks.shape), amp_dtype, criterion,
+                       id(getattr(optimizer, "ema", None)), id(optimizer), id(reducer))
                 g = cache.get(key)
                 if g is None:
                     g = cache[key] = _GraphedTrain(model, optimizer, criterion, amp_dtype, reducer)
@@ -455,6 +483,15 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
             history["skipped_steps"].append(sk)
         test_loss, test_dice, test_iou, test_cd, test_ci = evaluate_model(model, test_loader, criterion, device,
                                                                           amp_dtype=amp_dtype, graph=use_graph, per_class=True)
+        ema_cd = ema_ci = None
+        if ema is not None:
+            # the averaged weights swapped in: the swap leaves the shadows current, so the cached eval
+            # graph's sync_shadows finds nothing to cast; the trained weights are back bit for bit after
+            with ema.applied():
+                ema_loss, ema_dice, ema_iou, ema_cd, ema_ci = evaluate_model(
+                    model, test_loader, criterion, device, amp_dtype=amp_dtype, graph=use_graph, per_class=True)
+            for k, v in (("ema_test_loss", ema_loss), ("ema_test_dice", ema_dice), ("ema_test_iou", ema_iou)):
+                history[k].append(v)
         if scheduler is not None:
             scheduler.step(test_loss)
             if hasattr(optimizer, "sync_lr"):   # FusedAdamW: the device lr a captured step reads
@@ -463,12 +500,12 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
         for k, v in zip(history, (train_loss, train_dice, train_iou, test_loss, test_dice, test_iou, current_lr)):
             history[k].append(v)
         for k, v in (("train_class_dice", train_cd), ("train_class_iou", train_ci), ("test_class_dice", test_cd),
-                     ("test_class_iou", test_ci)):
+                     ("test_class_iou", test_ci), ("ema_test_class_dice", ema_cd), ("ema_test_class_iou", ema_ci)):
             if v is not None:       # multi-class runs only: a binary history keeps exactly its keys
                 history.setdefault(k, []).append(v)
         if checkpoint_path is not None:
             from .report import save_checkpoint
-            save_checkpoint(checkpoint_path, model, optimizer, scheduler, epoch + 1, history)
+            save_checkpoint(checkpoint_path, model, optimizer, scheduler, epoch + 1, history, ema=ema)
         if verbose and rank0:
             print(f'\n{"=" * 70}\nEpoch {epoch + 1}/{num_epochs}:')
             print(f"  [TRAIN] Loss: {train_loss:.4f} | Dice: {train_dice:.4f} | IoU: {train_iou:.4f}")
@@ -477,24 +514,33 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     return history
 
 
-def make_optimizer(model, lr=1e-4, weight_decay=1e-4, capturable=False, max_grad_norm=None, skip_nonfinite=False):
+def make_optimizer(model, lr=1e-4, weight_decay=1e-4, capturable=False, max_grad_norm=None, skip_nonfinite=False,
+                   ema_decay=None, ema_warmup=True):
     """AdamW as in cswin:937-941.  On the GPU: csu.optim.FusedAdamW (one csu_adamw_step launch for
     all 463 tensors; ``capturable=True`` reads lr/step from device tensors so the step can live in a
     HIP graph); on the CPU: torch.optim.AdamW.
     ``max_grad_norm`` (not in the reference): clip the global L2 gradient norm before every update --
     fused into FusedAdamW's step on the GPU; on the CPU the value is set as ``opt.max_grad_norm`` and
     train_step calls torch's clip_grad_norm_.  ``skip_nonfinite``: skip a step whose gradient norm
-    is inf / NaN (GPU only)."""
+    is inf / NaN (GPU only).
+    ``ema_decay`` (not in the reference): keep a csu.ema.WeightEMA(model, ema_decay, ema_warmup) of the
+    weights as ``opt.ema`` -- updated inside FusedAdamW's step launch on the GPU; on the CPU train_step
+    calls ``ema.update()`` after ``optimizer.step()``.  train_model evaluates and checkpoints it."""
     if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
         raise ValueError(f"invalid max_grad_norm {max_grad_norm} (None: no clipping)")
+    ema = None
+    if ema_decay is not None:
+        from .ema import WeightEMA
+        ema = WeightEMA(model, decay=ema_decay, warmup=ema_warmup)
     if next(model.parameters()).is_cuda:
         from .optim import FusedAdamW
         return FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=capturable,
-                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema=ema)
     if skip_nonfinite:
         raise ValueError("make_optimizer(skip_nonfinite=True) needs csu.optim.FusedAdamW (a model on the GPU)")
     opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
     opt.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+    opt.ema = ema
     return opt
 
 
@@ -596,6 +642,7 @@ class GraphedTrainStep:
             self.reducer.finish()
         _clip_for(self.opt)      # FusedAdamW: nothing here, its step() clips (captured with it)
         self.opt.step()
+        _ema_for(self.opt)       # FusedAdamW: nothing here either, the EMA rides in its step()
         return loss.detach(), out.detach()
 
     def __call__(self, x, t):

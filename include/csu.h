@@ -558,6 +558,37 @@ int csu_adamw_step_ex(const csu_adamw_item* items, int count, long total_chunks,
                       const float* ctl, int skip_nonfinite, int l2, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Exponential moving average (EMA) of the weights over a csu_adamw_item table and a parallel DEVICE
+ * array `ema` of fp32 pointers, one per item in item order (NULL: no EMA for that item; each EMA
+ * tensor has the item's numel, contiguous and 16-B aligned):
+ *     ema <- ema + (1 - d) (param - ema),   d = warmup ? min(decay, n / (n + 9)) : decay
+ * where n = *ema_updates_dev counts the EMA updates including this one (a device fp32 scalar the
+ * caller increments before the launch; may be NULL without warmup).  No atomics, fixed order: bitwise
+ * repeatable.  Replaces a Python ModelEma's per-tensor launches / torch._foreach_lerp_.
+ *
+ * csu_adamw_step_ema: csu_adamw_step_ex with the EMA update of every item done from the updated
+ *   parameter while it is in registers (+ 8 B per parameter, no extra launch).  ctl == NULL: no
+ *   clipping (csu_adamw_step / csu_adam_l2_step by l2).  A skipped step (skip_nonfinite != 0 and
+ *   ctl[2] == 0) leaves the EMA untouched too; the caller then adds ctl[2] instead of 1 to n.
+ *   Parameters, moments and shadows are bitwise those of the step without an EMA.
+ * csu_ema_update: the stand-alone update in one launch (for optimizers other than csu's); reads only
+ *   param, numel, chunk0 and the tile fields of the items.  csu_adamw_step_ema equals the plain step
+ *   followed by it bit for bit.
+ * csu_ema_swap: param <-> ema for every element in one launch, and every bf16 shadow layout the item
+ *   names re-made from the value now in param, exactly as the step writes them: evaluate on the
+ *   averaged weights in place, with every captured pointer still valid.  Swapping twice restores
+ *   parameters, EMA and shadows bit for bit.  Replaces a second model or two load_state_dict round
+ *   trips (each followed by a csu_cast_bf16_batch re-cast).
+ * ------------------------------------------------------------------------------------- */
+int csu_adamw_step_ema(const csu_adamw_item* items, int count, long total_chunks, const float* lr_dev, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const float* step_dev, float step,
+                       const float* ctl, int skip_nonfinite, int l2, float* const* ema, const float* ema_updates_dev,
+                       float ema_decay, int ema_warmup, void* stream);
+int csu_ema_update(const csu_adamw_item* items, float* const* ema, int count, long total_chunks,
+                   const float* ema_updates_dev, float decay, int warmup, void* stream);
+int csu_ema_swap(const csu_adamw_item* items, float* const* ema, int count, long total_chunks, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Dropout / DropPath (nn.Dropout cswin:190/193/512, timm DropPath cswin:344/367-368) as one
  * elementwise pass where no producing kernel fuses it:
  *   out[i] = res[i] + row_scale[(i / cols) / rows_per_sample] * keep(site, i) / (1 - p) * x[i]

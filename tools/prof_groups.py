@@ -20,7 +20,7 @@ GROUPS = [("head_fold_bwd", "carafe_head_bwd"), ("head_fold_fwd", "head_fold"), 
           ("maxpool2_bwd", "maxpool2_bwd"),
           ("carafe_head_fwd", "carafe_head_fwd"), ("carafe_head_bwd", "carafe_head_bwd"),
           ("carafe_fwd", "carafe_fwd"), ("carafe_bwd", "carafe_bwd"),
-          ("adamw_kernel", "adamw"), ("grad_sumsq", "grad_norm"), ("grad_norm_finish", "grad_norm"),
+          ("adamw_kernel", "adamw"), ("ema_update", "ema_update"), ("ema_swap", "ema_swap"), ("grad_sumsq", "grad_norm"), ("grad_norm_finish", "grad_norm"),
           ("grad_scale", "grad_scale"), ("cast_batch", "cast_bf16_batch"), ("colsum", "colsum"),
           ("simam_stats", "simam_fwd"), ("simam_apply", "simam_fwd"), ("simam_bwd", "simam_bwd"),
           ("head_fwd", "head_fwd"), ("head_bwd", "head_bwd"), ("gemm_f32", "gemm"), ("slab_sum", "gemm"),
