@@ -7,25 +7,12 @@
 // Per-image parameters are drawn on the host (csu.data.AugmentationTransform.draw, the
 // reference's np.random call order) and passed as a small device table.
 #include "common.hpp"
+#include "flipmap.hpp"
 
 namespace csu {
 namespace {
 
 constexpr int NT = 256;
-
-// pixel (y, x) of the rotated/flipped square image -> pixel of the stored image
-__device__ __forceinline__ void src_of(int S, int hflip, int vflip, int rot, int y, int x, int* sy, int* sx) {
-    // inverse rotation (rot = clockwise quarter turns applied after the flips)
-    int a = y, b = x;
-    if (rot == 1) { a = S - 1 - x; b = y; }          // R[y][x] = F[S-1-x][y]   (90 clockwise)
-    else if (rot == 2) { a = S - 1 - y; b = S - 1 - x; }
-    else if (rot == 3) { a = x; b = S - 1 - y; }     // R[y][x] = F[x][S-1-y]   (90 counter-clockwise)
-    // inverse flips: F = vflip(hflip(I))
-    if (vflip) a = S - 1 - a;
-    if (hflip) b = S - 1 - b;
-    *sy = a;
-    *sx = b;
-}
 
 // bilinear source coordinate of output index o for an n -> m resize (half-pixel centres, clamped
 // at the borders): integer part and weight of the upper neighbour

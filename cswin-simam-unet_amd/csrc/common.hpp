@@ -247,6 +247,20 @@ __device__ __forceinline__ void gelu_pair_fast(float x, float& g, float& dg) {
     dg = fmaf(x * 0.3989422804014327f, ex, phi);
 }
 
+constexpr float kLog2eLo = 1.92596299e-8f;   // log2(e) - (float)log2(e)
+
+// exp(x), x <= 0: v_exp_f32 of the product x log2(e) with the product's rounding error and the
+// constant's put back (relative error ~1 ulp over the whole range instead of |x| 2^-24).  Below
+// -200 the result is 0 in fp32 anyway; the clamp keeps x = -inf (a bucket's unused classes) out of
+// the error term, where inf - inf would make a NaN
+__device__ __forceinline__ float exp_neg(float x) {
+    x = fmaxf(x, -200.f);
+    const float h = x * kLog2e;
+    const float l = fmaf(x, kLog2e, -h) + x * kLog2eLo;
+    const float r = __builtin_amdgcn_exp2f(h);
+    return fmaf(r, l * kLn2, r);
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 template <bool V> using bconst = std::integral_constant<bool, V>;

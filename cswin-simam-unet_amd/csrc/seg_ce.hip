@@ -42,7 +42,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int CE_BLOCKS = 1024;
 constexpr int KMAX = 32;
-constexpr float kLog2eLo = 1.92596299e-8f;   // log2(e) - (float)log2(e)
 
 enum { MODE_CL = 0, MODE_NCHW = 1, MODE_GEN = 2 };
 
@@ -78,18 +77,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// exp(x), x <= 0: v_exp_f32 of the product x log2(e) with the product's rounding error and the
-// constant's put back (relative error ~1 ulp over the whole range instead of |x| 2^-24).  Below
-// -200 the result is 0 in fp32 anyway; the clamp keeps x = -inf (a bucket's unused classes) out of
-// the error term, where inf - inf would make a NaN
-__device__ __forceinline__ float exp_neg(float x) {
-    x = fmaxf(x, -200.f);
-    const float h = x * kLog2e;
-    const float l = fmaf(x, kLog2e, -h) + x * kLog2eLo;
-    const float r = __builtin_amdgcn_exp2f(h);
-    return fmaf(r, l * kLn2, r);
 }
 
 template <int V, typename T> __device__ __forceinline__ void loadv(const T* p, float* v) {

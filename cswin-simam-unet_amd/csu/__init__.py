@@ -15,6 +15,7 @@ from .losses import (MultiClassSegLoss, SegLoss, bce_dice_loss, ce_dice_loss, ce
                      tversky_loss)
 from .optim import FusedAdam, FusedAdamW
 from .ema import WeightEMA
+from .infer import (SlidingWindowPredictor, evaluate_full_res, plan_axis, plan_tiles, reference_predict, window_1d)
 from . import rng
 from .rng import manual_seed
 
@@ -22,4 +23,5 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "img2windows", "windows2img", "SimAM", "simam", "bce_loss", "dice_coefficient", "evaluate_model",
            "iou_score", "make_optimizer", "make_scheduler", "train_model", "train_step", "FusedAdamW", "FusedAdam",
            "rng", "manual_seed", "SegLoss", "dice_loss", "bce_dice_loss", "tversky_loss",
-           "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss", "WeightEMA"]
+           "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss", "WeightEMA",
+           "SlidingWindowPredictor", "reference_predict", "evaluate_full_res", "plan_axis", "plan_tiles", "window_1d"]

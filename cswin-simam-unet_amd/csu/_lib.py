@@ -210,6 +210,10 @@ _SIGS = {
     "csu_linear_wgrad_group": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "csu_augment_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "csu_tile_gather": (ctypes.c_int, [ctypes.c_int] * 5 + [c_void_p] * 4),
+    "csu_tile_blend": (ctypes.c_int, [ctypes.c_int] * 7 + [c_void_p] + [ctypes.c_long] * 3 + [ctypes.c_int]
+                       + [c_void_p] * 3 + [ctypes.c_int] * 4 + [c_void_p]),
+    "csu_tile_finish": (ctypes.c_int, [ctypes.c_int] * 3 + [c_void_p] * 3 + [c_float] + [c_void_p] * 3),
     "csu_bn_workspace": (c_size_t, [ctypes.c_long, ctypes.c_int]),
     "csu_bn_relu_fwd": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_float, c_float, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p,

@@ -877,6 +877,47 @@ int csu_augment_batch(int B, int S, const void* img, const void* mask, const int
                       float* out_mask, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Tiled whole-image inference (csrc/tile.hip): sliding-window prediction of an H x W image with a
+ * network of fixed S x S input, with test-time augmentation.  The reference has no counterpart.
+ *   table: int32 (B, 6) on the device, one record per batch slot: {y0, x0, hflip, vflip, clockwise
+ *      quarter turns 0..3 (applied after the flips, as csu_augment_batch), active}.  active = 0 marks
+ *      a padding slot of a ragged last batch.  (y0, x0) is the tile's top-left pixel in the image.
+ *   Pixel (y, x) of slot b's network input / output is tile pixel (ty, tx) = the stored-image pixel
+ *   of the augmentation's mapping for (hflip, vflip, rot), i.e. image pixel (y0 + ty, x0 + tx).
+ * csu_tile_gather: out fp32 (B, 3, S, S) from image uint8 (H, W, 3) (value / 255, an IEEE division)
+ *      or fp32 (3, H, W) (copied).  Coordinates outside the image are clamped to its edge, so an
+ *      image smaller than the tile is legal.  A padding slot gets slot 0's tile.
+ * csu_tile_blend: canvas[k, y0 + ty, x0 + tx] += w1[ty] w1[tx] p_k for every active slot, network
+ *      output pixel and class; canvas fp32 (K, H, W), w1 fp32 (S); pixels outside the canvas are
+ *      dropped, padding slots contribute nothing.  form CSU_TILE_PROB: z fp32, K = 1, p = z.
+ *      CSU_TILE_LOGITS: z fp32 or bf16 (upcast in registers), p = sigmoid(z) for K = 1, softmax over the
+ *      classes for 2 <= K <= 32 (max-subtracted, fp32).  Element (b, k, pix) of z is at z[b s_b + k s_k
+ *      + pix s_pix], pix = y S + x; class-last (s_k = 1) and NCHW (s_pix = 1) are read with vector
+ *      loads, anything else per element; pad_ok as in csu_seg_ce_fwd.  1 <= B <= 128 per launch.
+ *      Deterministic and order-preserving: no atomics; every canvas element receives its
+ *      contributions one at a time in table order, starting from its value on entry -- so a tile
+ *      list gives bitwise the same canvas however it is cut into launches.
+ *      Region [ry0, ry1) x [rx0, rx1): the part of the canvas the launch covers -- the bounding box of
+ *      the active slots' tiles, which the host knows from the table it made (0, 0, H, W: all of it).
+ *      Canvas pixels outside the region (rounded outwards to the kernel's patches) are not updated.
+ * csu_tile_finish: p = canvas / (ry[y] rx[x] n_tta) (ry (H), rx (W): the separable sum of the window
+ *      over the tile plan); prob fp32 (K, H, W) and labels uint8 (H, W), either may be NULL (not
+ *      both): label = p > 0.5 for K = 1, else argmax_k p with the lowest index winning a tie.
+ * All three take the stream and are capturable (no allocation, no synchronisation).
+ * CSU_E_ARG: a size < 1, B > 128 (blend), K < 1 or K > 32, an unknown src_kind, form or dtype, PROB with
+ *      K != 1 or bf16, a stride < 1, an empty region or one outside the canvas, n_tta <= 0, a null pointer.
+ * ------------------------------------------------------------------------------------- */
+enum csu_tile_src { CSU_TILE_SRC_U8_HWC = 0, CSU_TILE_SRC_F32_CHW = 1 };
+enum csu_tile_form { CSU_TILE_PROB = 0, CSU_TILE_LOGITS = 1 };
+int csu_tile_gather(int B, int S, int H, int W, int src_kind, const void* image, const int* table, float* out,
+                    void* stream);
+int csu_tile_blend(int B, int S, int H, int W, int K, int form, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                   int pad_ok, const int* table, const float* w1, float* canvas, int ry0, int rx0, int ry1, int rx1,
+                   void* stream);
+int csu_tile_finish(int K, int H, int W, const float* canvas, const float* ry, const float* rx, float n_tta, float* prob,
+                    void* labels, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plain-UNet BatchNorm2d (+ ReLU) and MaxPool2d(2) on NHWC rows (DoubleConv / Down,
  * train_unet_segmentation.py unet:177-204; replaces F.batch_norm + F.relu + F.max_pool2d there).
  * x, y: M = B*H*W rows of C channels (C % 8 == 0), dtype bf16 or f32 (y and dx in x's dtype).
