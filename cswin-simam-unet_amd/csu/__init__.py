@@ -16,6 +16,8 @@ from .losses import (MultiClassSegLoss, SegLoss, bce_dice_loss, ce_dice_loss, ce
 from .optim import FusedAdam, FusedAdamW
 from .ema import WeightEMA
 from .infer import (SlidingWindowPredictor, evaluate_full_res, plan_axis, plan_tiles, reference_predict, window_1d)
+from .metrics import (SurfaceMetrics, distance_transform_edt, reference_distance_transform_edt,
+                      reference_surface_metrics, surface_metrics)
 from . import rng
 from .rng import manual_seed
 
@@ -24,4 +26,6 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "iou_score", "make_optimizer", "make_scheduler", "train_model", "train_step", "FusedAdamW", "FusedAdam",
            "rng", "manual_seed", "SegLoss", "dice_loss", "bce_dice_loss", "tversky_loss",
            "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss", "WeightEMA",
-           "SlidingWindowPredictor", "reference_predict", "evaluate_full_res", "plan_axis", "plan_tiles", "window_1d"]
+           "SlidingWindowPredictor", "reference_predict", "evaluate_full_res", "plan_axis", "plan_tiles", "window_1d",
+           "SurfaceMetrics", "surface_metrics", "reference_surface_metrics", "distance_transform_edt",
+           "reference_distance_transform_edt"]

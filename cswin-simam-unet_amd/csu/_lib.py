@@ -214,6 +214,12 @@ _SIGS = {
     "csu_tile_blend": (ctypes.c_int, [ctypes.c_int] * 7 + [c_void_p] + [ctypes.c_long] * 3 + [ctypes.c_int]
                        + [c_void_p] * 3 + [ctypes.c_int] * 4 + [c_void_p]),
     "csu_tile_finish": (ctypes.c_int, [ctypes.c_int] * 3 + [c_void_p] * 3 + [c_float] + [c_void_p] * 3),
+    "csu_surface_workspace": (c_size_t, [ctypes.c_int] * 4),
+    "csu_surface_metrics": (ctypes.c_int, [ctypes.c_int] * 7 + [c_void_p, ctypes.c_int, c_void_p] + [ctypes.c_double] * 4
+                            + [c_void_p, c_size_t, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "csu_edt_workspace": (c_size_t, [ctypes.c_int] * 3),
+    "csu_edt": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_size_t,
+                                                    c_void_p, c_void_p]),
     "csu_bn_workspace": (c_size_t, [ctypes.c_long, ctypes.c_int]),
     "csu_bn_relu_fwd": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_float, c_float, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p,

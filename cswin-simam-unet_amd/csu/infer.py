@@ -416,12 +416,14 @@ class SlidingWindowPredictor:
         return (labels, prob) if return_prob else labels
 
 
-def evaluate_full_res(predictor, pairs: Iterable, num_classes: int = 1):
+def evaluate_full_res(predictor, pairs: Iterable, num_classes: int = 1, surface=None):
     """(Dice, IoU) of full-resolution hard predictions over ``pairs`` = (image, label map) items.
     Binary (num_classes = 1; a pixel is foreground where the map is > 0.5): the reference's
     batch-flattened formulas (cswin:692-708) per image, averaged over the images.  Multi-class: the
     per-class sums of all images, Dice and IoU as the macro means over the classes that occur
-    (csu.train._epoch_means)."""
+    (csu.train._epoch_means).  ``surface``: a csu.metrics.SurfaceMetrics accumulator; every
+    (prediction, label map) pair is also fed to it (on the prediction's device, without a
+    synchronisation) and the result is (Dice, IoU, surface.compute())."""
     from .train import _epoch_means
     K = int(num_classes)
     rows = []
@@ -429,6 +431,8 @@ def evaluate_full_res(predictor, pairs: Iterable, num_classes: int = 1):
         pred = predictor.predict(image)
         t = torch.as_tensor(np.asarray(target) if not isinstance(target, torch.Tensor) else target).to(pred.device)
         t = t.reshape(pred.shape)
+        if surface is not None:
+            surface.update(pred, t > 0.5 if K == 1 else t.long())
         if K == 1:
             p, tt = pred.to(torch.float64), (t > 0.5).to(torch.float64)
             rows.append(torch.stack([p.new_zeros(()), (p * tt).sum(), p.sum(), tt.sum()]))
@@ -438,4 +442,4 @@ def evaluate_full_res(predictor, pairs: Iterable, num_classes: int = 1):
             sums = torch.cat([(pm & tm).sum(1), pm.sum(1), tm.sum(1)]).double()
             rows.append(torch.cat([sums.new_zeros(1), sums]))
     _, dice, iou = _epoch_means(rows)
-    return dice, iou
+    return (dice, iou) if surface is None else (dice, iou, surface.compute())

@@ -918,6 +918,47 @@ int csu_tile_finish(int K, int H, int W, const float* canvas, const float* ry, c
                     void* labels, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Surface-distance metrics and an exact Euclidean distance transform (csrc/surface.hip).  The
+ * definitions are medpy's (metric.binary.hd / hd95 / assd, and the surface Dice); the reference has no
+ * counterpart.
+ *   pred, target: label maps (B, H, W), contiguous, uint8 or int64 each (they may differ), read in place.
+ *   For image b and class c (label value class0 + c; CSU_SURFACE_BINARY: C = 1 and a pixel is in the
+ *   mask where its value is > 0) P and T are the two masks, dP and dT their borders: the mask pixels
+ *   with at least one of the four edge neighbours outside the mask, everything beyond the image counting
+ *   as outside.  The distance between pixels is sqrt(sy^2 dy^2 + sx^2 dx^2).  d1 = for every pixel of dP
+ *   the distance to the nearest pixel of dT, d2 the same from dT to dP.
+ * csu_surface_metrics: out[(b out_classes + out_c0 + c) 6 ..] = fp64 {hd, hd95, assd, nsd, |dP|, |dT|}:
+ *      hd = max(max d1, max d2); hd95 = the `percentile`-th percentile of the pooled d1 and d2 with linear
+ *      interpolation (sorted v, h = (n - 1) q / 100, v[floor h] + (h - floor h)(v[floor h + 1] - v[floor h]));
+ *      assd = (mean d1 + mean d2) / 2; nsd = (#{d1 <= tolerance} + #{d2 <= tolerance}) / (|dP| + |dT|).
+ *      Where P or T is empty the first four are NaN.  out_classes / out_c0 let a caller fill a
+ *      (B, out_classes, 6) tensor in class chunks.
+ *      sy == sx: squared index distances in int32 (exact), scaled by s^2 in fp64, and d <= tolerance decided
+ *      as d2 s^2 <= tolerance^2; otherwise squared distances in fp32 (sy^2, sx^2 rounded to fp32).  Square
+ *      roots, sums and the percentile in fp64.  No floating-point atomics: block partials are combined in
+ *      a fixed order, so results are bitwise repeatable and do not depend on B, C or the chunking.
+ *      Workspace: csu_surface_workspace(B, C, H, W) bytes = B C (12 H W + 40 H) + O(B C) for tables, each
+ *      part rounded up to 256: per (image, class) two uint16 (H, W) column-distance fields, a list of up
+ *      to 2 H W 32-bit keys (one per border pixel), per-row partials and 4 x 2 x 256 histogram bins.
+ * csu_edt: out fp32 (B, H, W) = for every non-zero pixel of mask (B, H, W) the distance to the nearest
+ *      zero pixel, 0 at the zero pixels (scipy.ndimage.distance_transform_edt with sampling = (sy, sx));
+ *      inf everywhere in an image without a zero pixel.  Workspace csu_edt_workspace(B, H, W) = 2 B H W bytes.
+ * Both take the stream and are capturable (no allocation, no synchronisation).
+ * CSU_E_ARG: a size < 1, H or W > 32767, C > 32, B C 2 > 65535 (edt: B > 65535), an unknown mode or dtype,
+ *      BINARY with C != 1, a spacing that is not positive and finite, tolerance < 0, percentile outside
+ *      [0, 100], classes outside the out rows, a null pointer.  CSU_E_WORKSPACE: workspace too small.
+ * ------------------------------------------------------------------------------------- */
+enum csu_surface_dtype { CSU_SURFACE_U8 = 0, CSU_SURFACE_I64 = 1 };
+enum csu_surface_mode { CSU_SURFACE_LABELS = 0, CSU_SURFACE_BINARY = 1 };
+size_t csu_surface_workspace(int B, int C, int H, int W);
+int csu_surface_metrics(int B, int C, int H, int W, int mode, int class0, int pred_dtype, const void* pred,
+                        int target_dtype, const void* target, double sy, double sx, double tolerance, double percentile,
+                        void* workspace, size_t ws_bytes, double* out, int out_classes, int out_c0, void* stream);
+size_t csu_edt_workspace(int B, int H, int W);
+int csu_edt(int B, int H, int W, int dtype, const void* mask, double sy, double sx, void* workspace, size_t ws_bytes,
+            float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plain-UNet BatchNorm2d (+ ReLU) and MaxPool2d(2) on NHWC rows (DoubleConv / Down,
  * train_unet_segmentation.py unet:177-204; replaces F.batch_norm + F.relu + F.max_pool2d there).
  * x, y: M = B*H*W rows of C channels (C % 8 == 0), dtype bf16 or f32 (y and dx in x's dtype).
