@@ -234,6 +234,26 @@ __device__ __forceinline__ float xsum32(float x) {   // x + x of lane ^ 32
     return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
 }
 
+// LayerNorm-backward row phase (gemm_ws.hip WS_LNBWD, mlp.hip LNB): the sum over the LPR = 32 / 64 lanes
+// of a token row, on the VALU (DPP within the 16-lane rows, the permlane swaps across them), every lane
+// gets the sum; fixed association
+template <int LPR> __device__ __forceinline__ float ln_row_sum(float x) {
+    x = sum8_dpp(x);
+    x += dppf<0x128>(x);   // row_ror:8: lane i <- i ^ 8 of its 16-lane row
+    x = xsum16(x);
+    if constexpr (LPR == 64) x = xsum32(x);
+    return x;
+}
+// lane j (< 16) of v holds the value of the wave's row j: that of the lane's row RPI i + lane / (64 / RPI)
+template <int RPI> __device__ __forceinline__ float ln_row_val(float v, int i, int lane) {
+    const int b = __builtin_bit_cast(int, v);
+    if constexpr (RPI == 1) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, i));
+    else {
+        const int lo = __builtin_amdgcn_readlane(b, 2 * i), hi = __builtin_amdgcn_readlane(b, 2 * i + 1);
+        return __builtin_bit_cast(float, lane < 32 ? lo : hi);
+    }
+}
+
 __device__ __forceinline__ float gelu_fast(float x) {
     float ex;
     const float q = half_erfc_as(x, ex);

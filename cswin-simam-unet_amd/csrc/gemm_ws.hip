@@ -106,25 +106,6 @@ __device__ __forceinline__ bf16x8 e4m3x8_bf16(u32x2 w) {
     return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
-// WS_LNBWD row phase: the sum over the LPR = 32 / 64 lanes of a token row, on the VALU (DPP within the
-// 16-lane rows, the permlane swaps across them), every lane gets the sum; fixed association
-template <int LPR> __device__ __forceinline__ float ln_row_sum(float x) {
-    x = sum8_dpp(x);
-    x += dppf<0x128>(x);   // row_ror:8: lane i <- i ^ 8 of its 16-lane row
-    x = xsum16(x);
-    if constexpr (LPR == 64) x = xsum32(x);
-    return x;
-}
-// lane j (< 16) of v holds the value of the wave's row j: that of the lane's row RPI i + lane / (64 / RPI)
-template <int RPI> __device__ __forceinline__ float ln_row_val(float v, int i, int lane) {
-    const int b = __builtin_bit_cast(int, v);
-    if constexpr (RPI == 1) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, i));
-    else {
-        const int lo = __builtin_amdgcn_readlane(b, 2 * i), hi = __builtin_amdgcn_readlane(b, 2 * i + 1);
-        return __builtin_bit_cast(float, lane < 32 ? lo : hi);
-    }
-}
-
 // WS_LNBWD's LDS beside the token panel is its bf16 dh tile [64][N + 4] only; at N = 128 two workgroups
 // fit a CU's LDS and registers, so one's row phase runs beside the other's main loop
 constexpr int ws_ep_floats(int n, int epi) { return epi == WS_LNBWD ? WS_BM * (n + 4) / 2 : 4 * WS_BM * 36; }

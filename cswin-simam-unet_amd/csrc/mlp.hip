@@ -1042,6 +1042,105 @@ __global__ __launch_bounds__(2 * MT) void mlp_fwd8_kernel(long M, const bf16* __
     }
 }
 
+// LNB mode of mlp_bwd8_kernel / mlp_bwd_deep: the Mlp's input x is the output of a LayerNorm (CSWinBlock
+// norm2, cswin:366-368), so instead of storing dX the workgroup (64 tokens x all C features) runs that
+// LayerNorm's backward on it, as gemm_ws.hip's WS_LNBWD epilogue does for norm1: dX is rounded to bf16
+// exactly as the plain kernel stores it (the unfused path's numerics) into an LDS tile [64][C + 4] that
+// aliases the weight ring (dead after the last chunk), then each wave handles whole token rows with the
+// arithmetic of ln_bwd (layernorm.hip): dx = dres + rstd (g - mean(g) - xhat mean(g xhat)), g = dX * gamma,
+// row sums inside the wave, row-contiguous stores, and the block's dgamma / dbeta column partials (the
+// waves summed in wave order through LDS) into row blockIdx.x of part [M / 64][2C]
+// (csu_layernorm_param_reduce_batch's layout).  The x / dres rows are loaded in the row layout during
+// the main loop.  M % 64 == 0.
+struct MlpLnb {
+    const float* x;      // LayerNorm input (M, C) fp32
+    const float* gamma;  // (C)
+    const float* mean;   // (M)
+    const float* rstd;   // (M)
+    const float* dres;   // (M, C) fp32 gradient of the residual branch, or NULL
+    float* dx;           // (M, C)
+    bf16* dxb;           // (M, C) bf16 copy of dx
+    float* part;         // [M / 64][2C]
+};
+
+// Row layout of the LNB row phase with NWV waves: wave w owns token rows NR w .. NR w + NR - 1 of the
+// panel, LPR = C / 4 lanes x 4 features per row, RPI rows per wave instruction, NI instructions.
+template <int C, int NWV>
+struct LnbRows {
+    static constexpr int LPR = C / 4, RPI = 64 / LPR, NR = BM / NWV, NI = NR / RPI;
+    static constexpr int DS = C + 4;                // bf16 row stride of the dX tile (8-B lane writes)
+    static constexpr int TILE = BM * DS;            // bf16 elements of the tile; the partials follow it
+    static __device__ __forceinline__ int row(int wave, int i, int lane) { return NR * wave + RPI * i + lane / LPR; }
+    static __device__ __forceinline__ int c0(int lane) { return 4 * (lane % LPR); }
+    // byte offset of the lane's 4 features of instruction i in an fp32 (64, C) panel
+    static __device__ __forceinline__ unsigned off4(int wave, int i, int lane) {
+        return (unsigned)(row(wave, i, lane) * C + c0(lane)) * 4;
+    }
+};
+
+// The row phase: dxt holds the workgroup's bf16 dX tile (complete: the caller's barrier), px / pr the
+// lane's x / dres values of its NI rows, gw its 4 gamma, mu / rs the mean / rstd of the wave's row
+// (lane & 15) in lanes 0 .. NR - 1.  One barrier (the column partials), all NWV waves take part.
+template <int C, int NWV>
+__device__ __forceinline__ void lnb_row_phase(const bf16* dxt, const MlpLnb& ln, long m0, long rows, int wave, int lane,
+                                              const float (*px)[4], const float (*pr)[4], const float* gw, float mu_l,
+                                              float rs_l) {
+    using L = LnbRows<C, NWV>;
+    static_assert(L::LPR == 32 || L::LPR == 64, "LNB: C = 128 or 256");
+    static_assert(L::NR <= 16 && L::NI * L::RPI == L::NR, "LNB: a wave's rows fit ln_row_val");
+    static_assert(L::TILE * 2 % 16 == 0, "LNB: the partials are 16-B aligned");
+    const int c0 = L::c0(lane);
+    const auto rs_dx = buf_rsrc(ln.dx + m0 * C, rows * C * 4);
+    const auto rs_dxb = buf_rsrc(ln.dxb + m0 * C, rows * C * 2);
+    float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < L::NI; ++i) {
+        const int row = L::row(wave, i, lane);
+        float dh[4], xh[4], gg[4], o[4];
+        load4(dxt + row * L::DS + c0, dh);
+        const float mu = ln_row_val<L::RPI>(mu_l, i, lane), rs = ln_row_val<L::RPI>(rs_l, i, lane);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            xh[e] = (px[i][e] - mu) * rs;
+            gg[e] = dh[e] * gw[e];
+            s1 += gg[e];
+            s2 += gg[e] * xh[e];
+            dg[e] += dh[e] * xh[e];
+            db[e] += dh[e];
+        }
+        s1 = ln_row_sum<L::LPR>(s1) / C;
+        s2 = ln_row_sum<L::LPR>(s2) / C;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = rs * (gg[e] - s1 - xh[e] * s2) + pr[i][e];
+        const unsigned off = (unsigned)(row * C + c0);
+        buf_st4(rs_dx, row < rows ? off * 4 : kOOB, o);
+        buf_st4bf(rs_dxb, row < rows ? off * 2 : kOOB, o);
+    }
+    // column partials: the wave's row halves (C = 128), then the waves in wave order through LDS
+    float* red = reinterpret_cast<float*>(const_cast<bf16*>(dxt) + L::TILE);   // [NWV][2][C]
+    if constexpr (L::RPI == 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            dg[e] += __shfl_xor(dg[e], 32, 64);
+            db[e] += __shfl_xor(db[e], 32, 64);
+        }
+    }
+    if (lane < L::LPR) {
+        store4(red + (wave * 2 + 0) * C + c0, dg);
+        store4(red + (wave * 2 + 1) * C + c0, db);
+    }
+    lds_sync();
+    float* prow = ln.part + (size_t)blockIdx.x * 2 * C;
+    for (int i = threadIdx.x; i < 2 * C; i += 64 * NWV) {
+        const int k = i / C, c = i % C;
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) s += red[(w * 2 + k) * C + c];
+        prow[i] = s;
+    }
+}
+
 // Backward at C = 256 with two waves per SIMD (mlp_bwd8_kernel; no dropout: DROP launches keep the
 // 4-wave kernel).  The 4-wave kernel holds x, dY (64 + 64 registers) and a C x 32 partial dX (128) per
 // wave, so at C = 256 it runs one wave per SIMD with no overlap between chunks (PIPE off); removing
@@ -1059,12 +1158,17 @@ __global__ __launch_bounds__(2 * MT) void mlp_fwd8_kernel(long M, const bf16* __
 // 64-hidden chunks for mlp_fwd8_kernel: 32-hidden chunks with the weight DMA three chunks ahead (a
 // 4-stage ring) measured no faster (38.6 vs 37.4 us isolated, mlp_fwd 1072-1079 vs 1038-1049 us/step
 // in the step: profiles/r08f_mlp_ablate.txt, r08f bench pairs)
+// LNB (MlpLnb above): dX is not stored; norm2's backward runs on it in a row phase after the last chunk.
+// The x rows of the row layout are loaded before the first chunk (32 registers through the loop), the
+// dres rows, gamma, mean and rstd in the last chunk after phase A, whose token fragments are dead then, so the
+// row phase waits for nothing but its own stores.
 constexpr int kFwd8Hc = 64;
-template <int C>
+template <int C, bool LNB = false>
 __global__ __launch_bounds__(2 * MT) void mlp_bwd8_kernel(long M, const bf16* __restrict__ X, const bf16* __restrict__ dY,
                                                           const bf16* __restrict__ W1, const float* __restrict__ b1,
                                                           const bf16* __restrict__ W2, bf16* __restrict__ dH,
-                                                          bf16* __restrict__ G, bf16* __restrict__ dX, long rpi) {
+                                                          bf16* __restrict__ G, bf16* __restrict__ dX, long rpi,
+                                                          MlpLnb ln = MlpLnb{}) {
     static_assert(C == 256, "mlp_bwd8: C = 256 (32 dX features per wave)");
     constexpr int NCH = 4 * C / HC;
     constexpr int IMG = HC * C;
@@ -1108,6 +1212,16 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd8_kernel(long M, const bf16* __
             }
         }
     }
+    // LNB: the row phase's operands in its layout (LnbRows); the x rows ahead of chunk 0's DMA in
+    // vmcnt's order, so the first chunk's wait covers them
+    using LR = LnbRows<C, NWV>;
+    static_assert(!LNB || (LR::TILE * 2 + NWV * 2 * C * 4 <= (int)sizeof(ring)), "mlp_bwd8: the dX tile aliases the ring");
+    float px[LNB ? LR::NI : 1][4], pr[LNB ? LR::NI : 1][4], ln_gw[4], ln_mu = 0.f, ln_rs = 0.f;
+    if constexpr (LNB) {
+        const auto rs_lx = buf_rsrc(ln.x + m0 * C, rows * C * 4);
+#pragma unroll
+        for (int i = 0; i < LR::NI; ++i) buf_ld4(rs_lx, LR::off4(wave, i, lane), px[i]);
+    }
     D1 d1;
     D2 d2;
     d1.init(C, wave, lane);
@@ -1126,7 +1240,11 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd8_kernel(long M, const bf16* __
     // phase B element of this thread: token tb, hidden 8 hb .. 8 hb + 7 of the chunk
     const int tb = threadIdx.x >> 3, hb = threadIdx.x & 7;
 
-    for (int j = 0; j < NCH; ++j) {
+    // LNB: two passes of the chunk loop, unrolled -- chunks 0 .. NCH - 2, then chunk NCH - 1 on its own, so
+    // that the row phase's late loads (pr) are not live through the loop beside the token fragments
+#pragma unroll
+    for (int pass = 0; pass < (LNB ? 2 : 1); ++pass)
+    for (int j = (pass ? NCH - 1 : 0); j < (LNB && !pass ? NCH - 1 : NCH); ++j) {
         const int jc = chk(j);
         // chunk j landed; after its DMA this thread issued only chunk j-1's two phase-B stores
         if (j == 0) vmwait<0>(); else vmwait<2>();
@@ -1192,6 +1310,17 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd8_kernel(long M, const bf16* __
             }
         }
         lds_sync();
+        if constexpr (LNB) {
+            if (pass) {
+                // last chunk, tf is dead: the dres rows (NULL: read as 0), gamma, mean / rstd of the wave's rows
+                const auto rs_lr = buf_rsrc(ln.dres ? ln.dres + m0 * C : nullptr, ln.dres ? rows * C * 4 : 0);
+#pragma unroll
+                for (int i = 0; i < LR::NI; ++i) buf_ld4(rs_lr, LR::off4(wave, i, lane), pr[i]);
+                load4(ln.gamma + LR::c0(lane), ln_gw);
+                ln_mu = ln.mean[m0 + LR::NR * wave + (lane & (LR::NR - 1))];
+                ln_rs = ln.rstd[m0 + LR::NR * wave + (lane & (LR::NR - 1))];
+            }
+        }
         // ---- phase B
         {
             const bf16x8 hv = frag(himg, moff<2 * HC>(tb, 8 * hb));
@@ -1228,6 +1357,22 @@ __global__ __launch_bounds__(2 * MT) void mlp_bwd8_kernel(long M, const bf16* __
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], bf[1][s], acc[1], 0, 0, 0);
             }
         }
+    }
+    if constexpr (LNB) {
+        // every wave is past its last reads of the ring (no DMA is in flight: chunk NCH - 1 issues none):
+        // the bf16 dX tile over it, then the row phase
+        lds_sync();
+        bf16* dxt = ring;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float v[4] = {acc[tt][4 * g], acc[tt][4 * g + 1], acc[tt][4 * g + 2], acc[tt][4 * g + 3]};
+                store4(dxt + (32 * tt + r) * LR::DS + fo + 8 * g + 4 * h, v);
+            }
+        lds_sync();
+        lnb_row_phase<C, NWV>(dxt, ln, m0, rows, wave, lane, px, pr, ln_gw, ln_mu, ln_rs);
+        return;
     }
     // dX: lane holds token 32 tt + r, features fo + 8 g + 4 h + 0..3
     const auto rs_dx = buf_rsrc(dX + m0 * C, rows * C * 2);
@@ -1274,7 +1419,7 @@ int bwd_launch(long M, const void* x, const void* dy, const void* w1, const floa
     const auto dH = (bf16*)dh, G = (bf16*)g, dX = (bf16*)dx;
     const MlpDrop dd = d ? *d : MlpDrop{};
     if constexpr (C == 256) {   // two waves per SIMD; only dropout launches keep the 4-wave kernel
-        if (!d) mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi);
+        if (!d) mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi, MlpLnb{});
         else mlp_bwd_kernel<C, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
     } else {
         with_flag(d != nullptr, [&](auto df) {
@@ -2003,11 +2148,15 @@ template <int N> __device__ __forceinline__ void vmwait_le(int c) {   // s_waitc
 //   GEMM4  dx += W1c^T dh                    (A: transposed reads of the W1 image, k = the chunk's hidden
 //                                             features in the permuted order the accumulators give)
 // The wait for chunk j counts its younger DMAs and this wave's 4 stores per step since.
-template <int C, int RS, bool DROP>
+// LNB (MlpLnb above; no dropout): dX is not stored; norm2's backward runs on it in a row phase after the last
+// chunk.  Wave w's dX tokens 16 w .. 16 w + 15 are the rows it owns in the row phase; their x / dres rows
+// (64 registers), gamma, mean and rstd are loaded with the token operands, ahead of every DMA.
+template <int C, int RS, bool DROP, bool LNB = false>
 __global__ __launch_bounds__(MT) void mlp_bwd_deep(long M, const bf16* __restrict__ X, const bf16* __restrict__ dY,
                                                    const bf16* __restrict__ W1, const float* __restrict__ b1,
                                                    const bf16* __restrict__ W2, bf16* __restrict__ dH, bf16* __restrict__ G,
-                                                   bf16* __restrict__ dX, MlpDrop dd, long rpi) {
+                                                   bf16* __restrict__ dX, MlpDrop dd, long rpi, MlpLnb ln = MlpLnb{}) {
+    static_assert(!LNB || !DROP, "mlp_bwd_deep: the LayerNorm-backward mode has no dropout");
     constexpr int HD = 32;
     constexpr int NCH = 4 * C / HD;
     constexpr int KS = C / 32;
@@ -2044,6 +2193,21 @@ __global__ __launch_bounds__(MT) void mlp_bwd_deep(long M, const bf16* __restric
             __builtin_memcpy(&xf[s2], &a, 16);
             __builtin_memcpy(&yf[s2], &b, 16);
         }
+    }
+    using LR = LnbRows<C, MT / 64>;
+    static_assert(!LNB || (LR::TILE * 2 + MT / 64 * 2 * C * 4 <= (int)sizeof(ring)), "mlp_bwd_deep: the dX tile aliases the ring");
+    float px[LNB ? LR::NI : 1][4], pr[LNB ? LR::NI : 1][4], ln_gw[4], ln_mu = 0.f, ln_rs = 0.f;
+    if constexpr (LNB) {
+        const auto rs_lx = buf_rsrc(ln.x + m0 * C, rows * C * 4);
+        const auto rs_lr = buf_rsrc(ln.dres ? ln.dres + m0 * C : nullptr, ln.dres ? rows * C * 4 : 0);   // null: reads 0
+#pragma unroll
+        for (int i = 0; i < LR::NI; ++i) {
+            buf_ld4(rs_lx, LR::off4(wave, i, lane), px[i]);
+            buf_ld4(rs_lr, LR::off4(wave, i, lane), pr[i]);
+        }
+        load4(ln.gamma + LR::c0(lane), ln_gw);
+        ln_mu = ln.mean[m0 + LR::NR * wave + (lane & (LR::NR - 1))];
+        ln_rs = ln.rstd[m0 + LR::NR * wave + (lane & (LR::NR - 1))];
     }
     D1 d1;
     D2 d2;
@@ -2122,6 +2286,21 @@ __global__ __launch_bounds__(MT) void mlp_bwd_deep(long M, const bf16* __restric
         for (int ot = 0; ot < OT; ++ot)
             acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr16p<2 * C>(w1c, 16 * ot, 0, lane), db, acc[ot], 0, 0, 0);
     }
+    if constexpr (LNB) {
+        // the re-fetch DMAs still write the ring: drained by every wave before the barrier after which the
+        // bf16 dX tile goes over it (lane: token 16 wave + l16, features 16 ot + 4 kg + 0..3)
+        vmwait<0>();
+        lds_sync();
+        bf16* dxt = ring;
+#pragma unroll
+        for (int ot = 0; ot < OT; ++ot) {
+            const float v[4] = {acc[ot][0], acc[ot][1], acc[ot][2], acc[ot][3]};
+            store4(dxt + tok * LR::DS + 16 * ot + 4 * kg, v);
+        }
+        lds_sync();
+        lnb_row_phase<C, MT / 64>(dxt, ln, m0, rows, wave, lane, px, pr, ln_gw, ln_mu, ln_rs);
+        return;
+    }
     const auto rs_dx = buf_rsrc(dX + m0 * C, rows * C * 2);
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) {
@@ -2131,6 +2310,9 @@ __global__ __launch_bounds__(MT) void mlp_bwd_deep(long M, const bf16* __restric
     vmwait<0>();
 }
 
+// ring stages of the deep-ring kernels (csu_mlp_*_ex cfg 1, or cfg 2 = DEEPER)
+template <int C, bool DEEPER> constexpr int kDeepRs = DEEPER ? (C == 64 ? 8 : C == 128 ? 6 : 3) : (C == 64 ? 6 : 4);
+
 template <int C, int RS>
 int bwd_deep_launch(long M, const void* x, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
                     void* dx, const MlpDrop* d, long rpi, hipStream_t st) {
@@ -2138,9 +2320,25 @@ int bwd_deep_launch(long M, const void* x, const void* dy, const void* w1, const
     const MlpDrop dd = d ? *d : MlpDrop{};
     with_flag(d != nullptr, [&](auto df) {
         mlp_bwd_deep<C, RS, decltype(df)::value><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
-                                                                      (const bf16*)w2, (bf16*)dh, (bf16*)g, (bf16*)dx, dd, rpi);
+                                                                      (const bf16*)w2, (bf16*)dh, (bf16*)g, (bf16*)dx, dd, rpi,
+                                                                      MlpLnb{});
     });
     return check_launch("mlp_bwd (deep)");
+}
+
+// The Mlp backward with norm2's LayerNorm backward in its row phase (LNB): C = 128 the deep ring, C = 256 the
+// 8-wave kernel -- the kernels csu_mlp_bwd_dp runs at those widths
+template <int C>
+int bwd_ln_launch(long M, const void* h, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
+                  long rpi, const MlpLnb& ln, hipStream_t st) {
+    const dim3 grid((unsigned)(M / BM));
+    const auto X = (const bf16*)h, dY = (const bf16*)dy, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
+    if constexpr (C == 256)
+        mlp_bwd8_kernel<C, true><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, (bf16*)dh, (bf16*)g, nullptr, rpi, ln);
+    else
+        mlp_bwd_deep<C, kDeepRs<C, false>, false, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, (bf16*)dh, (bf16*)g, nullptr,
+                                                                            MlpDrop{}, rpi, ln);
+    return check_launch("mlp_bwd_ln");
 }
 
 }  // namespace
@@ -2194,9 +2392,6 @@ static int dispatch_c(const char* name, int C, int code, F&& f) {
     }
 }
 
-// ring stages of the deep-ring kernels (csu_mlp_*_ex cfg 1, or cfg 2 = DEEPER)
-template <int C, bool DEEPER> constexpr int kDeepRs = DEEPER ? (C == 64 ? 8 : C == 128 ? 6 : 3) : (C == 64 ? 6 : 4);
-
 extern "C" int csu_mlp_fwd_dp(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                               const float* res, float* out, const csu_mlp_dropout* d, void* stream) {
     MlpArgs a;
@@ -2237,6 +2432,21 @@ extern "C" int csu_mlp_bwd_dp(long M, int C, const void* x, const void* dy, cons
         if constexpr (CC == 128) return bwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
         else return bwd_launch<CC>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
     });
+}
+
+extern "C" int csu_mlp_bwd_ln_supported(long M, int C) { return (C == 128 || C == 256) && M >= BM && M % BM == 0; }
+
+extern "C" int csu_mlp_bwd_ln(long M, int C, const void* h, const void* dy, const void* w1, const float* b1, const void* w2,
+                              void* dh, void* g, long rows_per_image, const float* x, const float* gamma, const float* mean,
+                              const float* rstd, const float* dres, float* dx, void* dx_bf16, float* part, void* stream) {
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_bwd_ln", {h, dy, w1, b1, w2, dh, g, x, gamma, mean, rstd, dx, dx_bf16, part}, M, C, nullptr,
+                               stream, a))
+        return e;
+    if (!csu_mlp_bwd_ln_supported(M, C)) return fail(CSU_E_ARG, "mlp_bwd_ln: C must be 128 or 256 and M a multiple of 64");
+    const MlpLnb ln{x, gamma, mean, rstd, dres, dx, (bf16*)dx_bf16, part};
+    if (C == 128) return bwd_ln_launch<128>(M, h, dy, w1, b1, w2, dh, g, rows_per_image, ln, a.st);
+    return bwd_ln_launch<256>(M, h, dy, w1, b1, w2, dh, g, rows_per_image, ln, a.st);
 }
 
 extern "C" int csu_mlp_bwd(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,

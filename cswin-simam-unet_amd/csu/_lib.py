@@ -256,6 +256,8 @@ _SIGS = {
                                       c_void_p, ctypes.POINTER(MlpDropout), c_void_p]),
     "csu_mlp_bwd_dp": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, ctypes.POINTER(MlpDropout), c_void_p]),
+    "csu_mlp_bwd_ln_supported": (ctypes.c_int, [ctypes.c_long, ctypes.c_int]),
+    "csu_mlp_bwd_ln": (ctypes.c_int, [ctypes.c_long, ctypes.c_int] + [c_void_p] * 7 + [ctypes.c_long] + [c_void_p] * 9),
     "csu_mlp_bwd_wgrad_supported": (ctypes.c_int, [ctypes.c_int]),
     "csu_mlp_bwd_wgrad_workspace": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.POINTER(c_size_t),
                                                    ctypes.POINTER(c_size_t)]),

@@ -255,7 +255,6 @@ class CSWinBlock(nn.Module):
         else:
             y = ops.linear(att, self.proj.weight, self.proj.bias)
             x = ops.dropout(y, 0.0, 0, row_scale=rs1, rows_per_sample=L, residual=xa) if rs1 is not None else xa + y
-        xb, h2 = ops.layer_norm_fork(x, n2.weight, n2.bias, n2.eps, cd)
         if fused:
             # fc1 -> GELU -> [dropout] -> fc2 -> [dropout, DropPath] + residual (csrc/mlp.hip)
             md = None
@@ -263,7 +262,13 @@ class CSWinBlock(nn.Module):
                 md = ops.MlpDrop(snap, self.mlp._site_h, self.mlp._site_o, p_mlp, rs2, L)
             nn1 = getattr(self, "_next_norm", None)   # the next block's norm1: computed in the Mlp's epilogue
             ln_next = (nn1.weight, nn1.bias, nn1.eps) if nn1 is not None and cd == torch.bfloat16 else None
+            if cd == torch.bfloat16:   # norm2 backward inside the fused Mlp backward
+                y = ops.ln_mlp_residual(x, n2, self.mlp.fc1, self.mlp.fc2, md, ln_next)
+                if y is not None:
+                    return y
+            xb, h2 = ops.layer_norm_fork(x, n2.weight, n2.bias, n2.eps, cd)
             return ops.mlp_residual(xb, h2, self.mlp.fc1, self.mlp.fc2, md, ln_next=ln_next)
+        xb, h2 = ops.layer_norm_fork(x, n2.weight, n2.bias, n2.eps, cd)
         return self.mlp.forward_residual(h2, xb, rs2, L, snap)
 
 

@@ -2753,6 +2753,131 @@ def ln_linear_ws(x: torch.Tensor, ln: torch.nn.LayerNorm, lin: torch.nn.Linear):
         return _LnLinearWsFn.apply(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, wf, wtf, pre)
 
 
+class _LnMlpResidualFn(torch.autograd.Function):
+    """Residual junction + LayerNorm + fused Mlp (bf16): x -> x + Mlp(LN(x)) for CSWinBlock's norm2 -> Mlp
+    (cswin:368) at C = 128 / 256, no dropout.  Forward: exactly the launches of layer_norm_fork +
+    mlp_residual -- the LayerNorm (or the values the proj GEMM's epilogue already computed, _ln_pre) and
+    csu_mlp_fwd_ln / csu_mlp_fwd_dp.  Backward: ONE csu_mlp_bwd_ln launch recomputes h, writes dh and g for
+    the weight gradients and runs the norm2 backward on the Mlp's input gradient in its row phase (dx = dy +
+    LN'(bf16(dX)), its bf16 copy and the dgamma / dbeta block partials) -- dX never reaches HBM and the
+    LayerNorm-backward launch is gone.  The ledger charges the fused launch to "mlp_bwd": "layernorm_bwd"
+    falls and "mlp_bwd" rises by it."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps: float, w1, b1, w2, b2, w1c, w2c, pre, ln=None):
+        x = x.contiguous()
+        C = x.shape[-1]
+        M = x.numel() // C
+        g = gamma.detach().float().contiguous()
+        if pre is not None:
+            h2, mean, rstd = pre[3].view(M, C), pre[4], pre[5]
+        else:
+            b = beta.detach().float().contiguous()
+            h2 = torch.empty(M, C, dtype=torch.bfloat16, device=x.device)
+            mean = torch.empty(M, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+            _launch("layernorm_fwd", lambda: lib().csu_layernorm_fwd(M, C, float(eps), dtype_code(x), ptr(x), ptr(g),
+                                                                     ptr(b), CSU_BF16, ptr(h2), ptr(mean), ptr(rstd),
+                                                                     stream_ptr(x.device)),
+                    8 * M * C, M * C * (4 + 2) + M * 8, prec="f32")
+        res2 = x.view(M, C)
+        b1f = b1.detach().float().contiguous()
+        b2f = b2.detach().float().contiguous()
+        y = torch.empty_like(res2)
+        rpi = x.shape[1] if x.dim() == 3 else M   # rows per image: the kernel's hidden-chunk rotation
+        dd = ctypes.byref(_mlp_desc(None, rpi))
+        if ln is not None:
+            gf, bf_, eps1, h1, mean1, rstd1, stash = _mlp_ln_side(ln, M, C, x.device)
+            _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_ln(M, C, ptr(h2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
+                                                            ptr(y), dd, ptr(gf), ptr(bf_), eps1, ptr(h1), ptr(mean1),
+                                                            ptr(rstd1), stream_ptr(x.device)),
+                    16 * M * C * C + 8 * M * C, M * C * (2 + 4 + 4 + 2) + 16 * C * C + 8 * M)
+            _LN_STASH[0] = stash
+        else:
+            _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_dp(M, C, ptr(h2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
+                                                            ptr(y), dd, stream_ptr(x.device)),
+                    16 * M * C * C, M * C * (2 + 4 + 4) + 16 * C * C)
+        ctx.rpi = rpi
+        ctx.save_for_backward(x, g, mean, rstd, h2, w1c, b1f, w2c)
+        ctx.params = (gamma, beta)
+        ctx.pdtypes = (gamma.dtype, beta.dtype)
+        ctx.mlp = (w1, b1, w2, b2)
+        ctx.mmeta = (w1.dtype, b1.dtype, w2.dtype, b2.dtype)
+        _note_use(ctx, gamma, beta, w1, b1, w2, b2)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, mean, rstd, h2, w1c, b1f, w2c = ctx.saved_tensors
+        w1dt, b1dt, w2dt, b2dt = ctx.mmeta
+        M, C = h2.shape
+        dev = x.device
+        dyb = _bf16_of(dy).reshape(M, C).contiguous()    # the Mlp's dY
+        dres = dy.float().contiguous()                   # the residual branch's gradient: dy itself
+        dh = torch.empty(M, 4 * C, dtype=torch.bfloat16, device=dev)
+        gl = torch.empty_like(dh)
+        dx = torch.empty_like(x)
+        dxb = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
+        nblk = M // 64
+        work = torch.empty(nblk * 2 * C, dtype=torch.float32, device=dev)
+        _launch("mlp_bwd", lambda: lib().csu_mlp_bwd_ln(M, C, ptr(h2), ptr(dyb), ptr(w1c), ptr(b1f), ptr(w2c), ptr(dh), ptr(gl),
+                                                        ctx.rpi, ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx),
+                                                        ptr(dxb), ptr(work), stream_ptr(dev)),
+                24 * M * C * C + 12 * M * C,
+                # read once: h, dY, the weights, x, dres, mean / rstd, gamma; written once: dh, g, dx, its bf16 copy, part
+                M * C * (2 + 2) + M * 4 * C * (2 + 2) + 16 * C * C + M * C * (4 + 4) + M * 8 + C * 4 + M * C * (4 + 2)
+                + work.numel() * 4,
+                prec="bf16", tag=f"{M}x{C}:lnbwd")
+        dgb = _grad_dest(ctx.params)
+        if dgb is None:
+            dgb = torch.empty(2 * C, dtype=torch.float32, device=dev)
+        if not _ln_params(ctx, M, C, work, dgb, nblocks=nblk):
+            it = (_lib.LnParamItem * 1)()
+            it[0].workspace, it[0].dgamma, it[0].dbeta = work.data_ptr(), dgb.data_ptr(), dgb.data_ptr() + C * 4
+            it[0].rows, it[0].C, it[0].nblocks = M, C, nblk
+            _launch("layernorm_bwd", lambda: lib().csu_layernorm_param_reduce_batch(it, 1, stream_ptr(dev)),
+                    0, work.numel() * 4 + 2 * C * 4)
+        dw2, db2 = wgrad_maybe_side(dyb, gl, w2dt, b2dt, params=ctx.mlp[2:])
+        dw1, db1 = wgrad_maybe_side(dh, h2, w1dt, b1dt, params=ctx.mlp[:2])
+        dx._csu_bf16 = dxb
+        return (dx, dgb[:C].to(ctx.pdtypes[0]), dgb[C:].to(ctx.pdtypes[1]), None, dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt),
+                db2.to(b2dt), None, None, None, None)
+
+
+# the norm2 -> Mlp pair with the LayerNorm backward in the fused Mlp backward's row phase (csu_mlp_bwd_ln:
+# the Mlp's input gradient is never written and the norm2 ln_bwd launch is gone, DESIGN §6).
+# CSU_FUSE_LN_MLP=0: the unfused launches (csu_mlp_bwd_dp + csu_layernorm_bwd), for A/B runs and tests.
+FUSE_LN_MLP = os.environ.get("CSU_FUSE_LN_MLP", "1") != "0"
+
+
+def ln_mlp_residual(x: torch.Tensor, ln: torch.nn.LayerNorm, fc1: torch.nn.Linear, fc2: torch.nn.Linear,
+                    drop: Optional[MlpDrop] = None, ln_next=None):
+    """x + fc2(gelu(fc1(ln(x)))) through _LnMlpResidualFn (bf16 autocast, fp32 residual stream x, fp32
+    LayerNorm parameters, no dropout / DropPath, no fp8 weight format, a width and row count
+    csu_mlp_bwd_ln has), else None: the caller runs layer_norm_fork + mlp_residual.  ``ln_next`` as
+    mlp_residual's."""
+    C = x.shape[-1]
+    if not (FUSE_LN_MLP and FUSED_MLP and drop is None and _ACTIVE_FP8 is None and x.dtype == torch.float32
+            and fused_ok(x, C, fc1.out_features)):
+        return None
+    if (fc1.out_features != 4 * C or fc2.in_features != 4 * C or ln.weight.numel() != C
+            or ln.weight.dtype != torch.float32 or ln.bias.dtype != torch.float32):
+        return None
+    M = x.numel() // C
+    if not (lib().csu_mlp_supported(C) and lib().csu_mlp_bwd_ln_supported(M, C)):
+        return None
+    lnn = ln_next if (FUSE_NEXT_LN and ln_next is not None and ln_next[0].dtype == torch.float32
+                      and ln_next[0].numel() == C) else None
+    pre = _ln_pre(x, ln.weight, ln.bias, ln.eps, torch.bfloat16)
+    _LN_STASH[0] = None
+    with torch.autocast("cuda", enabled=False):
+        out = _LnMlpResidualFn.apply(x, ln.weight, ln.bias, ln.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                                     _weight_bf16(fc1.weight), _weight_bf16(fc2.weight), pre, lnn)
+    if lnn is not None:
+        _attach_ln(out)
+    return out
+
+
 # qkv in the fp8 weight format.  False: the bf16 weight-streaming GEMM on the EXACT dequantised e4m3
 # weight (the cast cache's shadow), norm1 in bf16 (fused into the previous block's Mlp epilogue where
 # it can be); True: e4m3 norm1 output x e4m3 weight on the fp8 MFMA (_LnLinearFp8Fn).  Measured at

@@ -652,6 +652,19 @@ int csu_mlp_fwd_dp(long M, int C, const void* x, const void* w1, const float* b1
                    const float* res, float* out, const csu_mlp_dropout* d, void* stream);
 int csu_mlp_bwd_dp(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
                    void* dh, void* g, void* dx, const csu_mlp_dropout* d, void* stream);
+/* csu_mlp_bwd_dp (no dropout) whose input h (M, C) bf16 is the output of a LayerNorm of x (CSWinBlock
+ * norm2, cswin:366-368: x + Mlp(LN(x))), with that LayerNorm's backward in the same launch: the Mlp's
+ * input gradient dX = dH W1 is not written; rounded to bf16 exactly as csu_mlp_bwd_dp stores it, it goes
+ * through dx (M, C) fp32 = dres + rstd (g - mean(g) - xhat mean(g xhat)), g = dX * gamma, xhat = (x - mean)
+ * rstd, its bf16 copy dx_bf16, and the dgamma / dbeta column partials of every 64-token block into part
+ * [M / 64][2C] (reduce them with csu_layernorm_param_reduce_batch, nblocks = M / 64).  x fp32 (M, C); dres
+ * fp32 (M, C) or NULL; dh and g (M, 4C) bf16 are bitwise csu_mlp_bwd_dp's; rows_per_image as
+ * csu_mlp_dropout.rows_per_sample (the hidden-chunk rotation).  Bitwise reproducible; no atomics.
+ * C = 128 or 256, M % 64 == 0 (csu_mlp_bwd_ln_supported). */
+int csu_mlp_bwd_ln_supported(long M, int C);
+int csu_mlp_bwd_ln(long M, int C, const void* h, const void* dy, const void* w1, const float* b1, const void* w2,
+                   void* dh, void* g, long rows_per_image, const float* x, const float* gamma, const float* mean,
+                   const float* rstd, const float* dres, float* dx, void* dx_bf16, float* part, void* stream);
 /* csu_mlp_bwd_dp that also forms the weight and bias gradients, so dh and g are never written
  * (C = 64 only: csu_mlp_bwd_wgrad_supported).  dx is bitwise csu_mlp_bwd_dp's.  Every workgroup of the
  * persistent launch accumulates dW1 = dh^T x, db1 = colsum(dh), dW2 = dy^T g, db2 = colsum(dy) over its
