@@ -73,8 +73,8 @@ class _StripeAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, geom: StripeGeometry, drop, *lepe):
         nb = len(geom.branches)
-        ws = [w.detach().float().contiguous() for w in lepe[:nb]]
-        bs = [b.detach().float().contiguous() for b in lepe[nb:]]
+        ws = [_f32(w) for w in lepe[:nb]]
+        bs = [_f32(b) for b in lepe[nb:]]
         require_device(qkv, *ws, *bs)
         qkv = qkv.contiguous()
         B, L, C3 = qkv.shape
@@ -360,18 +360,21 @@ def deferred_pending() -> bool:
     return bool(_LN_PENDING or _WG_DEFER or _WG_PENDING or _WG_POST or _LEPE_PENDING)
 
 
-def _ln_param_flush():
-    pend, _LN_PENDING[:] = list(_LN_PENDING), []
-    if not pend:
-        return
+def _ln_param_reduce(pend, nbytes):
+    """ONE csu_layernorm_param_reduce_batch launch over ``pend``: (partials workspace, [dgamma | dbeta]
+    destination, rows, C, partial rows) per LayerNorm; ``nbytes``: the launch's ledger bytes."""
     dev = pend[0][1].device
     items = (_lib.LnParamItem * len(pend))()
     for i, (work, dgb, rows, C, nblk) in enumerate(pend):
         items[i].workspace, items[i].dgamma, items[i].dbeta = work.data_ptr(), dgb.data_ptr(), dgb.data_ptr() + C * 4
         items[i].rows, items[i].C, items[i].nblocks = rows, C, nblk
-    nv = sum(2 * e[3] for e in pend)
-    _launch("layernorm_bwd", lambda: lib().csu_layernorm_param_reduce_batch(items, len(pend), stream_ptr(dev)),
-            0, sum(e[0].numel() for e in pend) + nv * 4)
+    _launch("layernorm_bwd", lambda: lib().csu_layernorm_param_reduce_batch(items, len(pend), stream_ptr(dev)), 0, nbytes)
+
+
+def _ln_param_flush():
+    pend, _LN_PENDING[:] = list(_LN_PENDING), []
+    if pend:
+        _ln_param_reduce(pend, sum(e[0].numel() for e in pend) + sum(2 * e[3] for e in pend) * 4)
 
 
 def _queue_flush():
@@ -427,6 +430,18 @@ def _ln_params(ctx, rows, C, work, dgb, nblocks=0):
     _late(ctx.params, (dgb[:C], dgb[C:]))
     _queue_flush()
     return True
+
+
+def _ln_param_grads(ctx, rows, C, work, nblk):
+    """(dgamma, dbeta) in the parameter dtypes from the ``nblk`` block partials a fused backward kernel
+    left in ``work``: reduced by the end-of-backward batch when allowed (_ln_params), else by a
+    one-item launch now."""
+    dgb = _grad_dest(ctx.params)
+    if dgb is None:
+        dgb = torch.empty(2 * C, dtype=torch.float32, device=work.device)
+    if not _ln_params(ctx, rows, C, work, dgb, nblocks=nblk):
+        _ln_param_reduce([(work, dgb, rows, C, nblk)], work.numel() * 4 + 2 * C * 4)
+    return dgb[:C].to(ctx.pdtypes[0]), dgb[C:].to(ctx.pdtypes[1])
 
 
 # Token-Linear weight gradients (bf16) of every Linear whose dW / db nothing reads before the end of
@@ -492,25 +507,31 @@ def _wgrad_deferrable(dy2, wdt, bdt, params) -> bool:
             and bdt in (None, torch.float32) and _deferrable(*params))
 
 
+def _ln_forward(x, weight, bias, eps, out_dtype, pre):
+    """(fp32 gamma, LN(x), mean, rstd) of a contiguous x: one csu_layernorm_fwd launch, or no launch
+    when a producing kernel's epilogue already computed the values (``pre``, see _ln_pre)."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    w = _f32(weight)
+    if pre is not None:
+        return w, pre[3].view(x.shape), pre[4], pre[5]
+    b = _f32(bias)
+    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    _launch("layernorm_fwd", lambda: lib().csu_layernorm_fwd(rows, C, float(eps), dtype_code(x), ptr(x), ptr(w), ptr(b),
+                                                             dtype_code(y), ptr(y), ptr(mean), ptr(rstd),
+                                                             stream_ptr(x.device)),
+            8 * rows * C, rows * C * (esize(x) + esize(y)) + rows * 8, prec=prec_of(x))
+    return w, y, mean, rstd
+
+
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps: float, out_dtype, pre=None):
         require_device(x, weight, bias)
         x = x.contiguous()
-        C = x.shape[-1]
-        rows = x.numel() // C
-        w = weight.detach().float().contiguous()
-        if pre is not None:   # computed by the producing fused Mlp (csu_mlp_fwd_ln)
-            y, mean, rstd = pre[3].view(x.shape), pre[4], pre[5]
-        else:
-            b = bias.detach().float().contiguous()
-            y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-            mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-            _launch("layernorm_fwd", lambda: lib().csu_layernorm_fwd(rows, C, float(eps), dtype_code(x), ptr(x), ptr(w),
-                                                                     ptr(b), dtype_code(y), ptr(y), ptr(mean), ptr(rstd),
-                                                                     stream_ptr(x.device)),
-                    8 * rows * C, rows * C * (esize(x) + esize(y)) + rows * 8, prec=prec_of(x))
+        w, y, mean, rstd = _ln_forward(x, weight, bias, eps, out_dtype, pre)
         ctx.save_for_backward(x, w, mean, rstd)
         ctx.pdtypes = (weight.dtype, bias.dtype)
         ctx.params = (weight, bias)
@@ -520,31 +541,8 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype not in (torch.float32, torch.bfloat16):
-            dy = dy.float()
-        C = x.shape[-1]
-        rows = x.numel() // C
-        dx = torch.empty_like(x)
-        # fp32 input (the residual stream under norm / norm_up, cswin:554/602): the bf16 copy of dx
-        # the upstream Mlp / GEMM backward consumes, written by the same pass (see _bf16_of)
-        dxb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if x.dtype == torch.float32 else None
-        dgb = _grad_dest(ctx.params)   # contiguous: one reduction pass
-        if dgb is None:
-            dgb = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-        dg, db = dgb[:C], dgb[C:]
-        L = lib()
-        nbytes = L.csu_layernorm_bwd_workspace(rows, C)
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
-        late = _ln_params(ctx, rows, C, work, dgb)
-        pg, pb = (None, None) if late else (ptr(dg), ptr(db))
-        _launch("layernorm_bwd", lambda: L.csu_layernorm_bwd_ex(rows, C, dtype_code(x), ptr(x), ptr(w), ptr(mean), ptr(rstd),
-                                                                dtype_code(dy), ptr(dy), None, ptr(dx), ptr(dxb), pg, pb,
-                                                                ptr(work), nbytes, stream_ptr(x.device)),
-                12 * rows * C, rows * C * (2 * esize(x) + esize(dy) + esize(dxb)) + rows * 8, prec=prec_of(x))
-        if dxb is not None:
-            dx._csu_bf16 = dxb
-        return dx, dg.to(ctx.pdtypes[0]), db.to(ctx.pdtypes[1]), None, None, None
+        dx, dg, db = _ln_fork_backward(ctx, x, w, mean, rstd, None, dy)
+        return dx, dg, db, None, None, None
 
 
 def _ln_pre(x, weight, bias, eps, od):
@@ -584,21 +582,7 @@ class _LayerNormForkFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, eps: float, out_dtype, pre=None):
         require_device(x, weight, bias)
         x = x.contiguous()
-        C = x.shape[-1]
-        rows = x.numel() // C
-        w = weight.detach().float().contiguous()
-        if pre is not None:
-            # computed by the producing fused Mlp's epilogue (csu_mlp_fwd_ln): no launch here
-            y, mean, rstd = pre[3].view(x.shape), pre[4], pre[5]
-        else:
-            b = bias.detach().float().contiguous()
-            y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-            mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-            _launch("layernorm_fwd", lambda: lib().csu_layernorm_fwd(rows, C, float(eps), dtype_code(x), ptr(x), ptr(w),
-                                                                     ptr(b), dtype_code(y), ptr(y), ptr(mean), ptr(rstd),
-                                                                     stream_ptr(x.device)),
-                    8 * rows * C, rows * C * (esize(x) + esize(y)) + rows * 8, prec=prec_of(x))
+        w, y, mean, rstd = _ln_forward(x, weight, bias, eps, out_dtype, pre)
         ctx.save_for_backward(x, w, mean, rstd)
         ctx.pdtypes = (weight.dtype, bias.dtype)
         ctx.params = (weight, bias)
@@ -615,7 +599,7 @@ class _LayerNormForkFn(torch.autograd.Function):
 def _ln_fork_backward(ctx, x, w, mean, rstd, dres, dy):
     """dx = dres + LN'(dy) in one csu_layernorm_bwd_ex pass (+ the bf16 copy of dx as
     ``_csu_bf16``), dgamma / dbeta (deferred into the batched reduction when allowed).  ctx carries
-    the LN parameters (``params``, ``pdtypes``)."""
+    the LN parameters (``params``, ``pdtypes``).  ``dres`` None: the plain LayerNorm backward."""
     C = x.shape[-1]
     rows = x.numel() // C
     if dy is None:
@@ -626,6 +610,8 @@ def _ln_fork_backward(ctx, x, w, mean, rstd, dres, dy):
     fp32 = x.dtype == torch.float32
     dres_k = dres.float().contiguous() if (dres is not None and fp32) else None
     dx = torch.empty_like(x)
+    # fp32 input (the residual stream, also under norm / norm_up, cswin:554/602): the bf16 copy of dx
+    # the upstream Mlp / GEMM backward consumes, written by the same pass (see _bf16_of)
     dxb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if fp32 else None
     L = lib()
     nbytes = L.csu_layernorm_bwd_workspace(rows, C)
@@ -707,7 +693,7 @@ class _HeadFn(torch.autograd.Function):
     def forward(ctx, x, w):
         require_device(x, w)
         x = x.contiguous()
-        wf = w.detach().float().contiguous().view(-1)
+        wf = _f32(w).view(-1)
         P, C = x.numel() // x.shape[-1], x.shape[-1]
         prob = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
         _launch("head_fwd", lambda: lib().csu_head_fwd(P, C, dtype_code(x), ptr(x), ptr(wf), ptr(prob), stream_ptr(x.device)),
@@ -742,7 +728,7 @@ class _CarafeHeadFn(torch.autograd.Function):
     def forward(ctx, x, enc, u, cb, H, W, s):
         require_device(x, enc, u, cb)
         x, enc = x.contiguous(), enc.to(x.dtype).contiguous()
-        uf, cf = u.detach().float().contiguous(), cb.detach().float().reshape(1).contiguous()
+        uf, cf = _f32(u), cb.detach().float().reshape(1).contiguous()
         B, C = x.shape[0], x.shape[-1]
         if x.numel() != B * H * W * C or enc.numel() != B * H * W * 9 * s * s:
             raise ValueError("carafe_head: x must be (B, H*W, C) and enc (B, H, W, 9 s^2)")
@@ -789,7 +775,7 @@ class _CarafeHeadFoldedFn(torch.autograd.Function):
         B, C = x.shape[0], x.shape[-1]
         O = w_out.shape[0]
         wo = w_out.detach().float().reshape(O, C).contiguous()
-        bo = b_out.detach().float().contiguous()
+        bo = _f32(b_out)
         wh = w_h.detach().float().reshape(O).contiguous()
         uf = torch.empty(C, dtype=torch.float32, device=x.device)
         cf = torch.empty(1, dtype=torch.float32, device=x.device)
@@ -1182,6 +1168,59 @@ def _weight_t(w, wc):
     return wt if wt is not None else wc.t().contiguous()
 
 
+def _cached(w, dtype):
+    """The active cast cache's ``dtype`` shadow of the weight w, or None."""
+    return _ACTIVE_CACHE.get(w, dtype) if _ACTIVE_CACHE is not None else None
+
+
+def _cached_conv(w, dtype):
+    """The active cast cache's (OHWI, IHWO) layouts of the conv weight w, or None."""
+    return _ACTIVE_CACHE.get_conv(w, dtype) if _ACTIVE_CACHE is not None else None
+
+
+def _weight_bf16(w):
+    wc = _cached(w, torch.bfloat16)
+    return wc if wc is not None else w.detach().to(torch.bfloat16).contiguous()
+
+
+def _f32(t):
+    """Detached contiguous fp32 copy of a parameter the kernels read as fp32 (a bias, a LayerNorm
+    gamma / beta); None stays None."""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _compute_dtype(x, *others):
+    """The dtype an op runs in: the autocast dtype for a device tensor under autocast, else the
+    promoted dtype of its operands."""
+    if x.is_cuda and torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    cd = x.dtype
+    for t in others:
+        cd = torch.promote_types(cd, t.dtype)
+    return cd
+
+
+def _token_gemm(x2, wc, w_frag, N, out_dtype, bias=None, resid=None):
+    """(M, N) = x2 (M, K) @ W^T (+ bias) (+ resid): csu_gemm_ws when the weight's fragment-ordered
+    operand ``w_frag`` (_ws_operand) exists and the shape is instantiated, else gemm4 on the (N, K)
+    natural layout ``wc``.  The input gradient is the same call on W^T's two layouts."""
+    M, K = x2.shape
+    if w_frag is not None and _ws_ok(M, N, K, out_dtype, resid=resid is not None):
+        return gemm_ws(x2, w_frag, N, out_dtype, bias=bias, resid=resid)
+    return gemm(x2, wc, False, out_dtype, bias=bias, resid=resid)
+
+
+def _linear_param_grads(needs, dy2, x2, wdt, bdt, params):
+    """(dW, db) of a Linear with an optional bias (``bdt`` None: none) in the parameter dtypes, from one
+    wgrad_maybe_side call; ``needs``: needs_input_grad of (weight, bias).  None for a gradient that is
+    not needed, and no launch when neither is."""
+    need_w, need_b = needs[0], bdt is not None and needs[1]
+    if not (need_w or need_b):
+        return None, None
+    dwf, dbf = wgrad_maybe_side(dy2, x2, wdt if need_w else None, bdt if need_b else None, params=params)
+    return dwf.to(wdt) if need_w else None, dbf.to(bdt) if need_b else None
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, cd, wc, odt=None):
@@ -1196,13 +1235,7 @@ class _LinearFn(torch.autograd.Function):
         ctx.wtf = None
         if ctx.fast:
             x2 = xc.reshape(-1, K).contiguous()
-            bf = None if bias is None else bias.detach().float().contiguous()
-            wf = _ws_operand(weight)
-            if wf is not None and _ws_ok(x2.shape[0], N, K, odt or cd):
-                y = gemm_ws(x2, wf, N, odt or cd, bias=bf)
-            else:
-                y = gemm(x2, wc, False, odt or cd, bias=bf)
-            y = y.view(*xc.shape[:-1], N)
+            y = _token_gemm(x2, wc, _ws_operand(weight), N, odt or cd, bias=_f32(bias)).view(*xc.shape[:-1], N)
             wt = _weight_t(weight, wc)
             ctx.wtf = _ws_operand(weight, True)
         elif cd == torch.float32 and K % 4 == 0 and N % 4 == 0:
@@ -1236,22 +1269,14 @@ class _LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if ctx.fast:
                 odt = xdt if xdt in (torch.float32, torch.bfloat16) else wc.dtype
-                if ctx.wtf is not None and _ws_ok(dy2.shape[0], K, N, odt):
-                    dx = gemm_ws(dy2, ctx.wtf, K, odt).view(xc.shape)
-                else:
-                    dx = gemm(dy2, wc, False, odt).view(xc.shape)
+                dx = _token_gemm(dy2, wc, ctx.wtf, K, odt).view(xc.shape)
             else:
                 dx = gemm_f32(1, dy2, wc.contiguous(), dy2.shape[0], K, N).view(xc.shape)
             if dx.dtype != xdt:
                 dx = dx.to(xdt)
         vec = 16 // dy2.element_size()
         if N % vec == 0 and K % vec == 0 and dy2.dtype in (torch.float32, torch.bfloat16):
-            dwf, dbf = wgrad_maybe_side(dy2, xc.reshape(-1, K), wdt if ctx.needs_input_grad[1] else None,
-                                        bdt if ctx.needs_input_grad[2] else None, params=ctx.params)
-            if ctx.needs_input_grad[1]:
-                dw = dwf.to(wdt)
-            if bdt is not None and ctx.needs_input_grad[2]:
-                db = dbf.to(bdt)
+            dw, db = _linear_param_grads(ctx.needs_input_grad[1:3], dy2, xc.reshape(-1, K), wdt, bdt, ctx.params)
             return dx, dw, db, None, None, None
         if ctx.needs_input_grad[1] or (bdt is not None and ctx.needs_input_grad[2]):
             # unreachable with the forward's width checks; no vendor-BLAS fallback
@@ -1606,7 +1631,7 @@ class _ConcatLinearFn(torch.autograd.Function):
         Ca, Cb, N = a.shape[-1], b.shape[-1], weight.shape[0]
         a2 = a.reshape(-1, Ca).contiguous()
         b2 = b.reshape(-1, Cb).contiguous()
-        bf = bias.detach().float().contiguous()
+        bf = _f32(bias)
         y1 = gemm(a2, wc[:, :Ca], False, torch.float32, bias=bf)
         y = gemm(b2, wc[:, Ca:], False, torch.float32, resid=y1)
         ctx.save_for_backward(a2, b2, _weight_t(weight, wc))
@@ -1638,10 +1663,8 @@ def concat_linear(a: torch.Tensor, b: torch.Tensor, weight: torch.Tensor, bias: 
     """fp32 Linear(cat([a, b], -1)) for bf16 a, b under bf16 autocast (see _ConcatLinearFn); other
     inputs take the reference form (cat, then linear with an fp32 output)."""
     Ca, Cb, N = a.shape[-1], b.shape[-1], weight.shape[0]
-    if (a.is_cuda and torch.is_autocast_enabled("cuda")
-            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and a.dtype == b.dtype == torch.bfloat16
-            and bias is not None and _gemm_ok(Ca, Cb, N)):
-        wc = _ACTIVE_CACHE.get(weight, torch.bfloat16) if _ACTIVE_CACHE is not None else None
+    if fused_ok(a, Ca, Cb, N) and a.dtype == b.dtype == torch.bfloat16 and bias is not None:
+        wc = _cached(weight, torch.bfloat16)
         if wc is None:
             wc = weight.to(torch.bfloat16)
         with torch.autocast("cuda", enabled=False):
@@ -1657,35 +1680,29 @@ class _LinearResidualFn(torch.autograd.Function):
         res2 = res.float().contiguous().view(-1, res.shape[-1])
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         M, K, N = x2.shape[0], x2.shape[1], wc.shape[0]
-        bf = bias.detach().float().contiguous()
+        bf = _f32(bias)
         wf = _ws_operand(weight)
         if (ln is not None and wf is not None and USE_GEMM_WS and K == N
                 and lib().csu_gemm_ws_ln_supported(M, N, K)):
             # + norm2 in the epilogue (csu_gemm_ws_ln), handed to the block's layer_norm_fork
-            gam, bet, eps = ln
-            gf, bf_ = gam.detach().float().contiguous(), bet.detach().float().contiguous()
+            gf, bf_, eps, h, mean, rstd, stash = _mlp_ln_side(ln, M, N, x2.device)
             y = torch.empty(M, N, dtype=torch.float32, device=x2.device)
-            h = torch.empty(M, N, dtype=torch.bfloat16, device=x2.device)
-            mean = torch.empty(M, dtype=torch.float32, device=x2.device)
-            rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
             if isinstance(wf, tuple):   # e4m3 weight fragments (fp8 format)
                 wq, sc, _ = wf
                 _launch("gemm", lambda: lib().csu_gemm_ws_ln_e4m3(M, N, ptr(x2), K, ptr(wq), ptr(sc), ptr(bf), ptr(res2),
-                                                                  ptr(y), ptr(gf), ptr(bf_), float(eps), ptr(h), ptr(mean),
+                                                                  ptr(y), ptr(gf), ptr(bf_), eps, ptr(h), ptr(mean),
                                                                   ptr(rstd), stream_ptr(x2.device)),
                         2 * M * N * K + 8 * M * N, M * K * 2 + N * K + M * N * (4 + 4 + 2) + 8 * M,
                         tag=f"{M}x{N}x{K}rbln:ws8")
             else:
                 _launch("gemm", lambda: lib().csu_gemm_ws_ln(M, N, ptr(x2), K, ptr(wf), ptr(bf), ptr(res2), ptr(y), ptr(gf),
-                                                             ptr(bf_), float(eps), ptr(h), ptr(mean), ptr(rstd),
+                                                             ptr(bf_), eps, ptr(h), ptr(mean), ptr(rstd),
                                                              stream_ptr(x2.device)),
                         2 * M * N * K + 8 * M * N, M * K * 2 + N * K * 2 + M * N * (4 + 4 + 2) + 8 * M,
                         tag=f"{M}x{N}x{K}rbln:ws")
-            _LN_STASH[0] = (gam, bet, float(eps), h, mean, rstd)
-        elif wf is not None and _ws_ok(M, N, K, torch.float32, resid=True):
-            y = gemm_ws(x2, wf, N, torch.float32, bias=bf, resid=res2)
+            _LN_STASH[0] = stash
         else:
-            y = gemm(x2, wc, False, torch.float32, bias=bf, resid=res2)
+            y = _token_gemm(x2, wc, wf, N, torch.float32, bias=bf, resid=res2)
         ctx.save_for_backward(x2, _weight_t(weight, wc))
         ctx.wtf = _ws_operand(weight, True)
         ctx.meta = (res.dtype, x.shape, weight.dtype, bias.dtype)
@@ -1697,12 +1714,8 @@ class _LinearResidualFn(torch.autograd.Function):
     def backward(ctx, dy):
         x2, wt = ctx.saved_tensors
         rdt, xshape, wdt, bdt = ctx.meta
-        dyb = _bf16_of(dy).view(-1, dy.shape[-1])
-        M, N, K = dyb.shape[0], dyb.shape[1], x2.shape[1]
-        if ctx.wtf is not None and _ws_ok(M, K, N, torch.bfloat16):
-            dx = gemm_ws(dyb.contiguous(), ctx.wtf, K, torch.bfloat16).view(xshape)
-        else:
-            dx = gemm(dyb, wt, False, torch.bfloat16).view(xshape)
+        dyb = _bf16_of(dy).view(-1, dy.shape[-1])   # contiguous either way (_bf16_of)
+        dx = _token_gemm(dyb, wt, ctx.wtf, x2.shape[1], torch.bfloat16).view(xshape)
         dw, db = wgrad_maybe_side(dyb, x2, wdt, bdt, params=ctx.params)
         return dy.to(rdt), dx, dw.to(wdt), db.to(bdt), None, None
 
@@ -1744,14 +1757,14 @@ class _MlpResidualFn(torch.autograd.Function):
         C = res.shape[-1]
         res2 = res.float().contiguous().view(-1, C)
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        h, g = gemm(x2, w1c, False, torch.bfloat16, bias=b1.detach().float().contiguous(), gelu_out=True)
+        h, g = gemm(x2, w1c, False, torch.bfloat16, bias=_f32(b1), gelu_out=True)
         if drop is None:
-            y = gemm(g, w2c, False, torch.float32, bias=b2.detach().float().contiguous(), resid=res2)
+            y = gemm(g, w2c, False, torch.float32, bias=_f32(b2), resid=res2)
         else:
             gd = torch.empty_like(g)
             _dropout_launch(g, None, gd, None, 1, drop.snap, drop.site_h, drop.p)
             g = gd
-            z = gemm(g, w2c, False, torch.bfloat16, bias=b2.detach().float().contiguous())
+            z = gemm(g, w2c, False, torch.bfloat16, bias=_f32(b2))
             y = torch.empty_like(res2)
             _dropout_launch(z, res2, y, drop.row_scale, drop.rps, drop.snap, drop.site_o, drop.p)
         ctx.save_for_backward(x2, h, g, _weight_t(w1, w1c), _weight_t(w2, w2c))
@@ -1781,11 +1794,6 @@ class _MlpResidualFn(torch.autograd.Function):
         return dy.to(rdt), dx, dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None, None
 
 
-def _weight_bf16(w):
-    wc = _ACTIVE_CACHE.get(w, torch.bfloat16) if _ACTIVE_CACHE is not None else None
-    return wc if wc is not None else w.detach().to(torch.bfloat16).contiguous()
-
-
 def fused_ok(x: torch.Tensor, *dims) -> bool:
     """True when the bf16 fused-GEMM path applies (CUDA, autocast bf16, 16-B aligned dims)."""
     return (x.is_cuda and torch.is_autocast_enabled("cuda")
@@ -1799,14 +1807,8 @@ def linear_residual(res, x, weight, bias, ln_next=None):
     """res + x @ W^T + b (fp32).  ``ln_next`` ((weight, bias, eps) of the LayerNorm that reads the
     result, CSWinBlock's norm2): computed in the same launch where gemm_ws has the shape and attached
     to the output for layer_norm_fork (``_csu_ln``)."""
-    ln = ln_next if (FUSE_PROJ_LN and ln_next is not None and ln_next[0].dtype == torch.float32
-                     and ln_next[0].numel() == weight.shape[0]) else None
-    _LN_STASH[0] = None
-    with torch.autocast("cuda", enabled=False):
-        out = _LinearResidualFn.apply(res, x, weight, bias, _weight_bf16(weight), ln)
-    if ln is not None:
-        _attach_ln(out)
-    return out
+    ln = _usable_ln_next(ln_next, weight.shape[0], FUSE_PROJ_LN)
+    return _apply_ln_stash(_LinearResidualFn, ln, res, x, weight, bias, _weight_bf16(weight), ln)
 
 
 def _mlp_desc(drop: Optional[MlpDrop], rpi: int):
@@ -1869,14 +1871,56 @@ def _mlp_bwd_wgrad(M, C, x2, dyb, w1c, b1f, w2c, dx, dd, dts, params):
 
 
 def _mlp_ln_side(ln, M, C, dev):
-    """Side outputs of a fused Mlp forward that also computes the next block's norm1 ``ln`` = (weight, bias,
-    eps): fp32 gamma, beta, eps, h1 (the bf16 LN output), mean, rstd, and the _LN_STASH tuple."""
+    """Side outputs of a forward launch (fused Mlp, proj GEMM) that also computes the LayerNorm ``ln`` = (weight,
+    bias, eps) of its (M, C) output: fp32 gamma, beta, eps, h1 (the bf16 LN output), mean, rstd, and the _LN_STASH
+    tuple."""
     gam, bet, eps = ln
     h1 = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
     mean = torch.empty(M, dtype=torch.float32, device=dev)
     rstd = torch.empty(M, dtype=torch.float32, device=dev)
-    return (gam.detach().float().contiguous(), bet.detach().float().contiguous(), float(eps), h1, mean, rstd,
-            (gam, bet, float(eps), h1, mean, rstd))
+    return (_f32(gam), _f32(bet), float(eps), h1, mean, rstd, (gam, bet, float(eps), h1, mean, rstd))
+
+
+def _mlp_rpi(x, M):
+    """Rows per image of a fused Mlp's (B, L, C) input: the kernel's hidden-chunk rotation, DropPath's sample."""
+    return x.shape[1] if x.dim() == 3 else M
+
+
+def _mlp_fwd_launch(M, C, x2, w1c, b1f, w2c, b2f, res2, y, drop, rpi, ln):
+    """The fused bf16 Mlp forward y = res2 + fc2(gelu(fc1(x2))) (+ ``drop``): csu_mlp_fwd_dp, or with ``ln``
+    (the next block's norm1 as (weight, bias, eps)) csu_mlp_fwd_ln, which also writes that LayerNorm of y
+    and leaves it in _LN_STASH for the caller's layer_norm_fork (_apply_ln_stash)."""
+    dev = x2.device
+    dd = ctypes.byref(_mlp_desc(drop, rpi))
+    flops, nbytes = 16 * M * C * C, M * C * (2 + 4 + 4) + 16 * C * C
+    if ln is None:
+        _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_dp(M, C, ptr(x2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
+                                                        ptr(y), dd, stream_ptr(dev)), flops, nbytes)
+        return
+    gf, bf_, eps, h1, mean, rstd, stash = _mlp_ln_side(ln, M, C, dev)
+    _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_ln(M, C, ptr(x2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2), ptr(y),
+                                                    dd, ptr(gf), ptr(bf_), eps, ptr(h1), ptr(mean), ptr(rstd),
+                                                    stream_ptr(dev)), flops + 8 * M * C, nbytes + M * C * 2 + 8 * M)
+    _LN_STASH[0] = stash
+
+
+def _mlp_fp8_fwd_launch(M, C, x2, ops8, b1f, b2f, res2, y, drop, rpi, ln):
+    """_mlp_fwd_launch on the e4m3 operands ``ops8`` (Fp8Weights.mlp_operands): csu_mlp_fp8_fwd / _fwd_ln."""
+    w1q, sw1, w2p, sw2 = ops8[:4]
+    dev = x2.device
+    dd = ctypes.byref(_mlp_desc(drop, rpi))
+    flops, nbytes = 16 * M * C * C, M * C * (2 + 4 + 4) + 8 * C * C
+    if ln is None:
+        _launch("mlp_fwd", lambda: lib().csu_mlp_fp8_fwd(M, C, ptr(x2), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2p), ptr(sw2),
+                                                         ptr(b2f), ptr(res2), ptr(y), dd, stream_ptr(dev)),
+                flops, nbytes, prec="fp8")
+        return
+    gf, bf_, eps, h1, mean, rstd, stash = _mlp_ln_side(ln, M, C, dev)
+    _launch("mlp_fwd", lambda: lib().csu_mlp_fp8_fwd_ln(M, C, ptr(x2), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2p), ptr(sw2),
+                                                        ptr(b2f), ptr(res2), ptr(y), dd, ptr(gf), ptr(bf_), eps, ptr(h1),
+                                                        ptr(mean), ptr(rstd), stream_ptr(dev)),
+            flops + 8 * M * C, nbytes + M * C * 2 + 8 * M, prec="fp8")
+    _LN_STASH[0] = stash
 
 
 def _mlp_fused_bwd(ctx, dy, x2, w1c, b1f, w2c, launch=None):
@@ -1922,26 +1966,11 @@ class _MlpFusedFn(torch.autograd.Function):
         C = x.shape[-1]
         res2 = res.float().contiguous().view(-1, C)
         x2 = x.reshape(-1, C).contiguous()
-        b1f = b1.detach().float().contiguous()
+        b1f, b2f = _f32(b1), _f32(b2)
         y = torch.empty_like(res2)
         M = x2.shape[0]
-        b2f = b2.detach().float().contiguous()
-        rpi = x.shape[1] if x.dim() == 3 else M   # rows per image: the kernel's hidden-chunk rotation
-        dd = ctypes.byref(_mlp_desc(drop, rpi))
-        if ln is not None:
-            # + the next block's norm1 on the output (csu_mlp_fwd_ln); handed to its layer_norm_fork
-            gf, bf_, eps, h1, mean, rstd, stash = _mlp_ln_side(ln, M, C, x2.device)
-            _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_ln(M, C, ptr(x2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
-                                                            ptr(y), dd, ptr(gf), ptr(bf_), eps, ptr(h1), ptr(mean),
-                                                            ptr(rstd), stream_ptr(x2.device)),
-                    16 * M * C * C + 8 * M * C, M * C * (2 + 4 + 4 + 2) + 16 * C * C + 8 * M)
-            _LN_STASH[0] = stash
-        else:
-            _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_dp(M, C, ptr(x2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
-                                                            ptr(y), dd, stream_ptr(x2.device)),
-                    16 * M * C * C, M * C * (2 + 4 + 4) + 16 * C * C)
-        ctx.drop = drop
-        ctx.rpi = rpi
+        ctx.drop, ctx.rpi = drop, _mlp_rpi(x, M)
+        _mlp_fwd_launch(M, C, x2, w1c, b1f, w2c, b2f, res2, y, drop, ctx.rpi, ln)
         ctx.save_for_backward(x2, w1c, b1f, w2c)
         ctx.meta = (res.dtype, x.shape, w1.dtype, b1.dtype, w2.dtype, b2.dtype)
         ctx.params = (w1, b1, w2, b2)
@@ -1979,6 +2008,25 @@ def _attach_ln(out):
         out._csu_ln = tuple(st) + (out._version,)
 
 
+def _usable_ln_next(ln_next, C, flag):
+    """``ln_next`` ((weight, bias, eps) of the LayerNorm that reads an op's (.., C) output) when the op
+    may compute it in its own launch -- ``flag`` (the caller's module switch) on, fp32 parameters of
+    width C -- else None."""
+    return ln_next if (flag and ln_next is not None and ln_next[0].dtype == torch.float32
+                       and ln_next[0].numel() == C) else None
+
+
+def _apply_ln_stash(fn, ln, *args):
+    """fn.apply(*args) outside autocast, for a Function whose forward leaves the LayerNorm of its output
+    in _LN_STASH when it computed one (``ln`` not None): attached to the output as ``_csu_ln``."""
+    _LN_STASH[0] = None
+    with torch.autocast("cuda", enabled=False):
+        out = fn.apply(*args)
+    if ln is not None:
+        _attach_ln(out)
+    return out
+
+
 # widths whose fp8 Mlp backward runs the fp8 kernel (csu_mlp_fp8_bwd); the others run the bf16 fused
 # backward on the dequantised (exact) bf16 shadows of the e4m3 weights -- faster at every width since
 # round 6: C = 64: 106 vs 120 us, C = 128: 64 vs 90 us per launch (profiles/r06d_step_breakdown_1024_fp8.txt),
@@ -2008,26 +2056,11 @@ class _MlpFp8Fn(torch.autograd.Function):
         x2 = x.reshape(-1, C).contiguous()
         if x2.dtype != torch.bfloat16:
             x2 = x2.to(torch.bfloat16)
-        w1q, sw1, w2p, sw2, w2t, w1tp = ops8
-        b1f = b1.detach().float().contiguous()
-        b2f = b2.detach().float().contiguous()
+        b1f, b2f = _f32(b1), _f32(b2)
         y = torch.empty_like(res2)
         M = x2.shape[0]
-        rpi = x.shape[1] if x.dim() == 3 else M
-        dd = ctypes.byref(_mlp_desc(drop, rpi))
-        if ln is not None:
-            # + the next block's norm1 on the output (csu_mlp_fp8_fwd_ln), as _MlpFusedFn
-            gf, bf_, eps, h1, mean, rstd, stash = _mlp_ln_side(ln, M, C, x2.device)
-            _launch("mlp_fwd", lambda: lib().csu_mlp_fp8_fwd_ln(M, C, ptr(x2), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2p), ptr(sw2),
-                                                                ptr(b2f), ptr(res2), ptr(y), dd, ptr(gf), ptr(bf_), eps,
-                                                                ptr(h1), ptr(mean), ptr(rstd), stream_ptr(x2.device)),
-                    16 * M * C * C + 8 * M * C, M * C * (2 + 4 + 4 + 2) + 8 * C * C + 8 * M, prec="fp8")
-            _LN_STASH[0] = stash
-        else:
-            _launch("mlp_fwd", lambda: lib().csu_mlp_fp8_fwd(M, C, ptr(x2), ptr(w1q), ptr(sw1), ptr(b1f), ptr(w2p), ptr(sw2),
-                                                             ptr(b2f), ptr(res2), ptr(y), dd, stream_ptr(x2.device)),
-                    16 * M * C * C, M * C * (2 + 4 + 4) + 8 * C * C, prec="fp8")
-        ctx.drop, ctx.rpi = drop, rpi
+        ctx.drop, ctx.rpi = drop, _mlp_rpi(x, M)
+        _mlp_fp8_fwd_launch(M, C, x2, ops8, b1f, b2f, res2, y, drop, ctx.rpi, ln)
         ctx.save_for_backward(x2, b1f)
         ctx.ops8 = ops8
         ctx.wc = (w1c, w2c)
@@ -2055,7 +2088,7 @@ class _MlpFp8Fn(torch.autograd.Function):
 def mlp_fp8(res, x, fc1: torch.nn.Linear, fc2: torch.nn.Linear, drop: Optional[MlpDrop] = None, ln=None):
     """The fp8 fused Mlp (_MlpFp8Fn) when the active fp8 weight format holds fc1 / fc2 as an Mlp pair
     (model.set_weight_format('fp8_e4m3') under bf16 autocast), else None.  ``ln``: (weight, bias, eps)
-    of the next block's norm1, computed in the same launch (left in _LN_STASH for the caller)."""
+    of the next block's norm1, computed in the same launch (attached to the output as ``_csu_ln``)."""
     if _ACTIVE_FP8 is None or not x.is_cuda or fc1.out_features != 4 * x.shape[-1] or fc2.in_features != fc1.out_features:
         return None
     ops8 = _ACTIVE_FP8.mlp_operands(fc1.weight, fc2.weight)
@@ -2064,8 +2097,7 @@ def mlp_fp8(res, x, fc1: torch.nn.Linear, fc2: torch.nn.Linear, drop: Optional[M
     w1c = w2c = None
     if x.shape[-1] not in FP8_MLP_BWD_C:   # the bf16 backward's operands: the exact dequantised shadows
         w1c, w2c = _weight_bf16(fc1.weight), _weight_bf16(fc2.weight)
-    with torch.autocast("cuda", enabled=False):
-        return _MlpFp8Fn.apply(res, x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ops8, drop, w1c, w2c, ln)
+    return _apply_ln_stash(_MlpFp8Fn, ln, res, x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ops8, drop, w1c, w2c, ln)
 
 
 # the fused one-launch Mlp where the library has it (C in {64, 128, 256}); otherwise two gemm4 launches
@@ -2082,24 +2114,14 @@ def mlp_residual(res, x, fc1: torch.nn.Linear, fc2: torch.nn.Linear, drop: Optio
     no dropout).  ``ln_next`` (the next block's norm1 as (weight, bias, eps)): its LayerNorm of the
     output is computed in the same launch and attached to the output for layer_norm_fork."""
     C = x.shape[-1]
-    ln = ln_next if (FUSE_NEXT_LN and ln_next is not None and ln_next[0].dtype == torch.float32
-                     and ln_next[0].numel() == C) else None
-    _LN_STASH[0] = None
+    ln = _usable_ln_next(ln_next, C, FUSE_NEXT_LN)
     y = mlp_fp8(res, x, fc1, fc2, drop, ln=None if FP8_QKV else ln)   # FP8_QKV: norm1 is the e4m3 LN
     if y is not None:
-        if ln is not None:
-            _attach_ln(y)
         return y
+    args = (res, x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, _weight_bf16(fc1.weight), _weight_bf16(fc2.weight), drop)
     if FUSED_MLP and fc1.out_features == 4 * C and lib().csu_mlp_supported(C):
-        with torch.autocast("cuda", enabled=False):
-            out = _MlpFusedFn.apply(res, x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, _weight_bf16(fc1.weight),
-                                    _weight_bf16(fc2.weight), drop, ln)
-        if ln is not None:
-            _attach_ln(out)
-        return out
-    with torch.autocast("cuda", enabled=False):
-        return _MlpResidualFn.apply(res, x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, _weight_bf16(fc1.weight),
-                                    _weight_bf16(fc2.weight), drop)
+        return _apply_ln_stash(_MlpFusedFn, ln, *args, ln)
+    return _apply_ln_stash(_MlpResidualFn, None, *args)
 
 
 # fp32 master weight (by storage address) -> (weakref to it, its CastCache, index in the cache,
@@ -2567,7 +2589,7 @@ def fp8_gemm(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Ten
     if wq.shape[1] != K or sa.numel() != M or sw.numel() != N or aq.dtype != torch.uint8 or wq.dtype != torch.uint8:
         raise ValueError("fp8_gemm: shape / dtype mismatch")
     aq, wq, sa, sw = aq.contiguous(), wq.contiguous(), sa.float().contiguous(), sw.float().contiguous()
-    b = None if bias is None else bias.detach().float().contiguous()
+    b = _f32(bias)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=aq.device)
     _launch("fp8_gemm", lambda: lib().csu_fp8_gemm(M, N, K, ptr(aq), ptr(sa), ptr(wq), ptr(sw), ptr(b), ptr(out),
                                                    stream_ptr(aq.device)),
@@ -2593,8 +2615,8 @@ def layer_norm_fp8(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ep
     x = x.contiguous()
     C = x.shape[-1]
     rows = x.numel() // C
-    w = weight.detach().float().contiguous()
-    b = bias.detach().float().contiguous()
+    w = _f32(weight)
+    b = _f32(bias)
     q = torch.empty(rows, C, dtype=torch.uint8, device=x.device)
     s = torch.empty(rows, dtype=torch.float32, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
@@ -2624,7 +2646,7 @@ class _LnLinearFp8Fn(torch.autograd.Function):
         C = x.shape[-1]
         hq, hs, mean, rstd, hdq = layer_norm_fp8(x, gamma, beta, eps, dq=True)
         y = fp8_gemm(hq, hs, wq, ws, bias).view(*x.shape[:-1], wq.shape[0])
-        ctx.save_for_backward(x, gamma.detach().float().contiguous(), mean, rstd, hdq, wt)
+        ctx.save_for_backward(x, _f32(gamma), mean, rstd, hdq, wt)
         ctx.params = (gamma, beta)
         ctx.pdtypes = (gamma.dtype, beta.dtype)
         ctx.lin = (weight, bias)
@@ -2641,11 +2663,7 @@ class _LnLinearFp8Fn(torch.autograd.Function):
             N = dy.shape[-1]
             dy2 = _bf16_of(dy).reshape(-1, N).contiguous()
             dh = gemm(dy2, wt, False, torch.bfloat16).view(x.shape)
-            need_w, need_b = ctx.needs_input_grad[3], bdt is not None and ctx.needs_input_grad[4]
-            if need_w or need_b:
-                dwf, dbf = wgrad_maybe_side(dy2, h, wdt if need_w else None, bdt if need_b else None, params=ctx.lin)
-                dw = dwf.to(wdt) if need_w else None
-                db = dbf.to(bdt) if need_b else None
+            dw, db = _linear_param_grads(ctx.needs_input_grad[3:5], dy2, h, wdt, bdt, ctx.lin)
         dx, dg, dbeta = _ln_fork_backward(ctx, x, g, mean, rstd, dres, dh)
         return dx, dg, dbeta, dw, db, None, None, None, None
 
@@ -2661,24 +2679,12 @@ class _LnLinearWsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, weight, bias, eps: float, wf, wtf, pre):
-        x = x.contiguous()
+        x = x.contiguous()    # fp32 (ln_linear_ws)
         C = x.shape[-1]
-        rows = x.numel() // C
-        g = gamma.detach().float().contiguous()
-        if pre is not None:
-            h1, mean, rstd = pre[3].view(x.shape), pre[4], pre[5]
-        else:
-            b = beta.detach().float().contiguous()
-            h1 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-            mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-            _launch("layernorm_fwd", lambda: lib().csu_layernorm_fwd(rows, C, float(eps), dtype_code(x), ptr(x), ptr(g),
-                                                                     ptr(b), CSU_BF16, ptr(h1), ptr(mean), ptr(rstd),
-                                                                     stream_ptr(x.device)),
-                    8 * rows * C, rows * C * (4 + 2) + rows * 8, prec="f32")
+        g, h1, mean, rstd = _ln_forward(x, gamma, beta, eps, torch.bfloat16, pre)
         N = weight.shape[0]
-        h2 = h1.view(rows, C)
-        y = gemm_ws(h2, wf, N, torch.bfloat16, bias=None if bias is None else bias.detach().float().contiguous())
+        h2 = h1.view(-1, C)
+        y = gemm_ws(h2, wf, N, torch.bfloat16, bias=_f32(bias))
         ctx.save_for_backward(x, g, mean, rstd, h2, wtf)
         ctx.params = (gamma, beta)
         ctx.pdtypes = (gamma.dtype, beta.dtype)
@@ -2710,23 +2716,10 @@ class _LnLinearWsFn(torch.autograd.Function):
                 rows * N * 2 + N * C * 2 + rows * C * (4 + (4 if dres_k is not None else 0)) + C * 4 + rows * 8
                 + rows * C * (4 + 2) + work.numel() * 4,
                 prec="bf16", tag=f"{rows}x{C}x{N}:lnbwd:ws")
-        dgb = _grad_dest(ctx.params)
-        if dgb is None:
-            dgb = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-        if not _ln_params(ctx, rows, C, work, dgb, nblocks=nblk):
-            it = (_lib.LnParamItem * 1)()
-            it[0].workspace, it[0].dgamma, it[0].dbeta = work.data_ptr(), dgb.data_ptr(), dgb.data_ptr() + C * 4
-            it[0].rows, it[0].C, it[0].nblocks = rows, C, nblk
-            _launch("layernorm_bwd", lambda: lib().csu_layernorm_param_reduce_batch(it, 1, stream_ptr(x.device)),
-                    0, work.numel() * 4 + 2 * C * 4)
-        dw = db = None
-        need_w, need_b = ctx.needs_input_grad[3], bdt is not None and ctx.needs_input_grad[4]
-        if need_w or need_b:
-            dwf, dbf = wgrad_maybe_side(dy2, h, wdt if need_w else None, bdt if need_b else None, params=ctx.lin)
-            dw = dwf.to(wdt) if need_w else None
-            db = dbf.to(bdt) if need_b else None
+        dg, dbeta = _ln_param_grads(ctx, rows, C, work, nblk)
+        dw, db = _linear_param_grads(ctx.needs_input_grad[3:5], dy2, h, wdt, bdt, ctx.lin)
         dx._csu_bf16 = dxb
-        return dx, dgb[:C].to(ctx.pdtypes[0]), dgb[C:].to(ctx.pdtypes[1]), dw, db, None, None, None, None
+        return dx, dg, dbeta, dw, db, None, None, None, None
 
 
 # the norm1 -> qkv pair on csu_gemm_ws with the LayerNorm backward in the input-gradient GEMM
@@ -2765,39 +2758,15 @@ class _LnMlpResidualFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps: float, w1, b1, w2, b2, w1c, w2c, pre, ln=None):
-        x = x.contiguous()
+        x = x.contiguous()    # fp32 (ln_mlp_residual)
         C = x.shape[-1]
         M = x.numel() // C
-        g = gamma.detach().float().contiguous()
-        if pre is not None:
-            h2, mean, rstd = pre[3].view(M, C), pre[4], pre[5]
-        else:
-            b = beta.detach().float().contiguous()
-            h2 = torch.empty(M, C, dtype=torch.bfloat16, device=x.device)
-            mean = torch.empty(M, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-            _launch("layernorm_fwd", lambda: lib().csu_layernorm_fwd(M, C, float(eps), dtype_code(x), ptr(x), ptr(g),
-                                                                     ptr(b), CSU_BF16, ptr(h2), ptr(mean), ptr(rstd),
-                                                                     stream_ptr(x.device)),
-                    8 * M * C, M * C * (4 + 2) + M * 8, prec="f32")
-        res2 = x.view(M, C)
-        b1f = b1.detach().float().contiguous()
-        b2f = b2.detach().float().contiguous()
+        g, h, mean, rstd = _ln_forward(x, gamma, beta, eps, torch.bfloat16, pre)
+        h2, res2 = h.view(M, C), x.view(M, C)
+        b1f, b2f = _f32(b1), _f32(b2)
         y = torch.empty_like(res2)
-        rpi = x.shape[1] if x.dim() == 3 else M   # rows per image: the kernel's hidden-chunk rotation
-        dd = ctypes.byref(_mlp_desc(None, rpi))
-        if ln is not None:
-            gf, bf_, eps1, h1, mean1, rstd1, stash = _mlp_ln_side(ln, M, C, x.device)
-            _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_ln(M, C, ptr(h2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
-                                                            ptr(y), dd, ptr(gf), ptr(bf_), eps1, ptr(h1), ptr(mean1),
-                                                            ptr(rstd1), stream_ptr(x.device)),
-                    16 * M * C * C + 8 * M * C, M * C * (2 + 4 + 4 + 2) + 16 * C * C + 8 * M)
-            _LN_STASH[0] = stash
-        else:
-            _launch("mlp_fwd", lambda: lib().csu_mlp_fwd_dp(M, C, ptr(h2), ptr(w1c), ptr(b1f), ptr(w2c), ptr(b2f), ptr(res2),
-                                                            ptr(y), dd, stream_ptr(x.device)),
-                    16 * M * C * C, M * C * (2 + 4 + 4) + 16 * C * C)
-        ctx.rpi = rpi
+        ctx.rpi = _mlp_rpi(x, M)
+        _mlp_fwd_launch(M, C, h2, w1c, b1f, w2c, b2f, res2, y, None, ctx.rpi, ln)
         ctx.save_for_backward(x, g, mean, rstd, h2, w1c, b1f, w2c)
         ctx.params = (gamma, beta)
         ctx.pdtypes = (gamma.dtype, beta.dtype)
@@ -2828,20 +2797,11 @@ class _LnMlpResidualFn(torch.autograd.Function):
                 M * C * (2 + 2) + M * 4 * C * (2 + 2) + 16 * C * C + M * C * (4 + 4) + M * 8 + C * 4 + M * C * (4 + 2)
                 + work.numel() * 4,
                 prec="bf16", tag=f"{M}x{C}:lnbwd")
-        dgb = _grad_dest(ctx.params)
-        if dgb is None:
-            dgb = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        if not _ln_params(ctx, M, C, work, dgb, nblocks=nblk):
-            it = (_lib.LnParamItem * 1)()
-            it[0].workspace, it[0].dgamma, it[0].dbeta = work.data_ptr(), dgb.data_ptr(), dgb.data_ptr() + C * 4
-            it[0].rows, it[0].C, it[0].nblocks = M, C, nblk
-            _launch("layernorm_bwd", lambda: lib().csu_layernorm_param_reduce_batch(it, 1, stream_ptr(dev)),
-                    0, work.numel() * 4 + 2 * C * 4)
+        dg, dbeta = _ln_param_grads(ctx, M, C, work, nblk)
         dw2, db2 = wgrad_maybe_side(dyb, gl, w2dt, b2dt, params=ctx.mlp[2:])
         dw1, db1 = wgrad_maybe_side(dh, h2, w1dt, b1dt, params=ctx.mlp[:2])
         dx._csu_bf16 = dxb
-        return (dx, dgb[:C].to(ctx.pdtypes[0]), dgb[C:].to(ctx.pdtypes[1]), None, dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt),
-                db2.to(b2dt), None, None, None, None)
+        return dx, dg, dbeta, None, dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None, None, None
 
 
 # the norm2 -> Mlp pair with the LayerNorm backward in the fused Mlp backward's row phase (csu_mlp_bwd_ln:
@@ -2866,16 +2826,10 @@ def ln_mlp_residual(x: torch.Tensor, ln: torch.nn.LayerNorm, fc1: torch.nn.Linea
     M = x.numel() // C
     if not (lib().csu_mlp_supported(C) and lib().csu_mlp_bwd_ln_supported(M, C)):
         return None
-    lnn = ln_next if (FUSE_NEXT_LN and ln_next is not None and ln_next[0].dtype == torch.float32
-                      and ln_next[0].numel() == C) else None
+    lnn = _usable_ln_next(ln_next, C, FUSE_NEXT_LN)
     pre = _ln_pre(x, ln.weight, ln.bias, ln.eps, torch.bfloat16)
-    _LN_STASH[0] = None
-    with torch.autocast("cuda", enabled=False):
-        out = _LnMlpResidualFn.apply(x, ln.weight, ln.bias, ln.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
-                                     _weight_bf16(fc1.weight), _weight_bf16(fc2.weight), pre, lnn)
-    if lnn is not None:
-        _attach_ln(out)
-    return out
+    return _apply_ln_stash(_LnMlpResidualFn, lnn, x, ln.weight, ln.bias, ln.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                           _weight_bf16(fc1.weight), _weight_bf16(fc2.weight), pre, lnn)
 
 
 # qkv in the fp8 weight format.  False: the bf16 weight-streaming GEMM on the EXACT dequantised e4m3
@@ -2895,7 +2849,7 @@ def ln_linear_fp8(x: torch.Tensor, ln: torch.nn.LayerNorm, lin: torch.nn.Linear)
     N, K = lin.weight.shape
     if got is None or N % 64 or K % 64 or K > 512:
         return None
-    wc = _ACTIVE_CACHE.get(lin.weight, torch.bfloat16) if _ACTIVE_CACHE is not None else None
+    wc = _cached(lin.weight, torch.bfloat16)
     if wc is None:
         return None
     wt = _weight_t(lin.weight, wc)      # (K, N) bf16 of the dequantised e4m3 weight: the dX GEMM's operand
@@ -2912,13 +2866,9 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     Contract (no vendor-BLAS fallback): device tensors; bf16 in / out features multiples of 8, fp32
     multiples of 4 -- anything else raises ``CsuError`` (callers with narrower layers zero-pad them,
     as the model's 1-class head does)."""
-    if x.is_cuda and torch.is_autocast_enabled("cuda"):
-        cd = torch.get_autocast_dtype("cuda")
-    else:
-        cd = torch.promote_types(x.dtype, weight.dtype)
-    wc = _ACTIVE_CACHE.get(weight, cd) if _ACTIVE_CACHE is not None else None
+    cd = _compute_dtype(x, weight)
     with torch.autocast("cuda", enabled=False):
-        return _LinearFn.apply(x, weight, bias, cd, wc, out_dtype)
+        return _LinearFn.apply(x, weight, bias, cd, _cached(weight, cd), out_dtype)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2987,7 +2937,7 @@ class _Conv2dFn(torch.autograd.Function):
             else:
                 xc = torch.zeros(B, H, W, cp, dtype=cd, device=x.device)
                 xc[..., :C] = x
-            cached = _ACTIVE_CACHE.get_conv(weight, cd) if _ACTIVE_CACHE is not None else None
+            cached = _cached_conv(weight, cd)
             if cached is not None and cached[0].shape[-1] == cp:
                 w_ohwi = cached[0]
             else:
@@ -2995,11 +2945,11 @@ class _Conv2dFn(torch.autograd.Function):
             cached = None
         else:
             xc = (x if x.dtype == cd else x.to(cd)).contiguous()
-            cached = _ACTIVE_CACHE.get_conv(weight, cd) if _ACTIVE_CACHE is not None else None
+            cached = _cached_conv(weight, cd)
             w_ohwi = cached[0] if cached else weight.detach().permute(0, 2, 3, 1).to(cd).contiguous()
         g = _conv_geom(B, H, W, cp, N, KH, KW, stride, pad)
         y = torch.empty(B, g.OH, g.OW, N, dtype=cd, device=x.device)
-        bf = None if bias is None else bias.detach().float().contiguous()
+        bf = _f32(bias)
         ws, nws = _conv_ws(0, g, xc)
         _launch("conv_fwd", lambda: lib().csu_conv2d_fwd_ws(ctypes.byref(g), dtype_code(xc), ptr(xc), ptr(w_ohwi), ptr(bf),
                                                             ptr(y), ptr(ws), nws, stream_ptr(x.device)),
@@ -3058,10 +3008,7 @@ class _Conv2dFn(torch.autograd.Function):
 def conv2d(x_nhwc: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int = 1,
            pad: int = 0) -> torch.Tensor:
     """nn.Conv2d on a channels-last (B, H, W, C) tensor -> (B, OH, OW, N); torch weight (N, C, KH, KW)."""
-    if x_nhwc.is_cuda and torch.is_autocast_enabled("cuda"):
-        cd = torch.get_autocast_dtype("cuda")
-    else:
-        cd = torch.promote_types(x_nhwc.dtype, weight.dtype)
+    cd = _compute_dtype(x_nhwc, weight)
     with torch.autocast("cuda", enabled=False):
         return _Conv2dFn.apply(x_nhwc, weight, bias, stride, pad, cd)
 
@@ -3078,10 +3025,10 @@ class _CatConv2dFn(torch.autograd.Function):
         B, H, W, Ca = xa.shape
         N, C, KH, KW = weight.shape
         g = _conv_geom(B, H, W, C, N, KH, KW, 1, pad)
-        cached = _ACTIVE_CACHE.get_conv(weight, cd) if _ACTIVE_CACHE is not None else None
+        cached = _cached_conv(weight, cd)
         w_ohwi = cached[0] if cached else weight.detach().permute(0, 2, 3, 1).to(cd).contiguous()
         y = torch.empty(B, g.OH, g.OW, N, dtype=cd, device=xa.device)
-        bf = None if bias is None else bias.detach().float().contiguous()
+        bf = _f32(bias)
         _launch("conv_fwd", lambda: lib().csu_conv2d_fwd_split(ctypes.byref(g), dtype_code(xa), ptr(xa), ptr(xb), Ca, ptr(w_ohwi),
                                                                ptr(bf), ptr(y), stream_ptr(xa.device)),
                 2 * y.numel() * KH * KW * C, (xa.numel() + xb.numel() + w_ohwi.numel() + y.numel()) * 2, prec=prec_of(xa))
@@ -3132,10 +3079,7 @@ def conv2d_cat(xa: torch.Tensor, xb: torch.Tensor, weight: torch.Tensor, bias: O
     """conv2d(torch.cat([xa, xb], -1), weight, bias, 1, pad) on channels-last tensors; the
     concatenation is never materialised when csu_conv2d_split_ok accepts the geometry (bf16),
     otherwise it is (and conv2d runs on it)."""
-    if xa.is_cuda and torch.is_autocast_enabled("cuda"):
-        cd = torch.get_autocast_dtype("cuda")
-    else:
-        cd = torch.promote_types(torch.promote_types(xa.dtype, xb.dtype), weight.dtype)
+    cd = _compute_dtype(xa, xb, weight)
     B, H, W, Ca = xa.shape
     N, C, KH, KW = weight.shape
     if Ca + xb.shape[-1] != C:
@@ -3160,7 +3104,7 @@ class _ConvTranspose2dFn(torch.autograd.Function):
         g = _conv_geom(B, OH, OW, C, N, KH, KW, stride, 0)
         w_ihwo = weight.detach().permute(1, 2, 3, 0).to(cd).contiguous()
         y = torch.empty(B, OH, OW, C, dtype=cd, device=x.device)
-        bf = None if bias is None else bias.detach().float().contiguous()
+        bf = _f32(bias)
         _launch("convT_fwd", lambda: lib().csu_conv2d_dgrad(ctypes.byref(g), dtype_code(xc), ptr(xc), ptr(w_ihwo), ptr(bf),
                                                             ptr(y), stream_ptr(x.device)),
                 2 * xc.numel() * KH * KW * C, (xc.numel() + w_ihwo.numel() + y.numel()) * xc.element_size(), prec=prec_of(xc))
@@ -3194,9 +3138,6 @@ class _ConvTranspose2dFn(torch.autograd.Function):
 def conv_transpose2d(x_nhwc: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                      stride: int) -> torch.Tensor:
     """nn.ConvTranspose2d(k, stride) with padding 0 on channels-last tensors."""
-    if x_nhwc.is_cuda and torch.is_autocast_enabled("cuda"):
-        cd = torch.get_autocast_dtype("cuda")
-    else:
-        cd = torch.promote_types(x_nhwc.dtype, weight.dtype)
+    cd = _compute_dtype(x_nhwc, weight)
     with torch.autocast("cuda", enabled=False):
         return _ConvTranspose2dFn.apply(x_nhwc, weight, bias, stride, cd)
