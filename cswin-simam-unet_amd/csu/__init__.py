@@ -18,6 +18,8 @@ from .ema import WeightEMA
 from .infer import (SlidingWindowPredictor, evaluate_full_res, plan_axis, plan_tiles, reference_predict, window_1d)
 from .metrics import (SurfaceMetrics, distance_transform_edt, reference_distance_transform_edt,
                       reference_surface_metrics, surface_metrics)
+from .components import (PostProcess, connected_components, postprocess_labels, reference_connected_components,
+                         reference_postprocess_labels)
 from . import rng
 from .rng import manual_seed
 
@@ -28,4 +30,5 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "MultiClassSegLoss", "ce_loss", "ce_dice_loss", "multiclass_dice_loss", "WeightEMA",
            "SlidingWindowPredictor", "reference_predict", "evaluate_full_res", "plan_axis", "plan_tiles", "window_1d",
            "SurfaceMetrics", "surface_metrics", "reference_surface_metrics", "distance_transform_edt",
-           "reference_distance_transform_edt"]
+           "reference_distance_transform_edt", "connected_components", "postprocess_labels", "PostProcess",
+           "reference_connected_components", "reference_postprocess_labels"]

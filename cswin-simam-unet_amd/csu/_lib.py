@@ -220,6 +220,11 @@ _SIGS = {
     "csu_edt_workspace": (c_size_t, [ctypes.c_int] * 3),
     "csu_edt": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_size_t,
                                                     c_void_p, c_void_p]),
+    "csu_ccl_workspace": (c_size_t, [ctypes.c_int] * 3),
+    "csu_ccl": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p, ctypes.c_int, c_void_p, c_size_t] + [c_void_p] * 4),
+    "csu_cc_filter_workspace": (c_size_t, [ctypes.c_int] * 3),
+    "csu_cc_filter": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_uint,
+                                                          ctypes.c_int, ctypes.c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "csu_bn_workspace": (c_size_t, [ctypes.c_long, ctypes.c_int]),
     "csu_bn_relu_fwd": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_float, c_float, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p,

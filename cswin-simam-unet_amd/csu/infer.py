@@ -25,6 +25,7 @@ TTA_VARIANTS = {
 D4 = tuple(TTA_VARIANTS)
 MAX_SLOTS = 128         # csu_tile_blend: slots per launch
 MAX_CLASSES = 32
+_OWN = object()         # predict(postprocess=...): the predictor's own setting
 
 
 def parse_tta(tta) -> List[Tuple[int, int, int]]:
@@ -327,15 +328,18 @@ class SlidingWindowPredictor:
     the fraction of a tile shared with its neighbour; ``window`` "gaussian" or "uniform"; ``tta`` a
     sequence of variant names / (hflip, vflip, rot) triples, or "d4"; ``batch_size`` tiles per forward
     (at most 128); ``amp_dtype``: run the forward under autocast; ``graph`` (None = automatic for the csu
-    models on a GPU): capture the batch forward once per (batch, dtype) and replay it.
+    models on a GPU): capture the batch forward once per (batch, dtype) and replay it.  ``postprocess``
+    (None: off): a csu.components.PostProcess, or any callable on a label map; ``predict`` then returns
+    the cleaned labels (the probabilities of ``return_prob`` are untouched).
 
     ``predict`` uploads the image and the whole tile table once, then launches gather -> forward ->
     blend per batch and one finish, with no host-device synchronisation in between.  The result is
     deterministic: the canvas does not depend on ``batch_size`` (csu_tile_blend keeps table order)."""
 
     def __init__(self, model, tile: int = None, overlap: float = 0.5, window: str = "gaussian", tta=("identity",),
-                 batch_size: int = 16, amp_dtype=None, graph=None, output: str = None):
+                 batch_size: int = 16, amp_dtype=None, graph=None, output: str = None, postprocess=None):
         self.model = model
+        self.postprocess = postprocess
         S = tile if tile is not None else getattr(model, "img_size", None)
         if S is None:
             raise ValueError("SlidingWindowPredictor: tile is required (the model has no img_size)")
@@ -364,9 +368,17 @@ class SlidingWindowPredictor:
         with torch.autocast(x.device.type, dtype=self.amp_dtype or torch.float32, enabled=self.amp_dtype is not None):
             return self.model(x)
 
-    def predict(self, image, return_prob: bool = False):
+    def predict(self, image, return_prob: bool = False, postprocess=_OWN):
         """uint8 labels (H, W) -- and fp32 probabilities (K, H, W) with ``return_prob`` -- on the model's
-        device, for a uint8 (H, W, 3) (numpy or tensor) or fp32 (3, H, W) image."""
+        device, for a uint8 (H, W, 3) (numpy or tensor) or fp32 (3, H, W) image.  ``postprocess``: applied to
+        the labels instead of the predictor's own setting for this call (None: nothing is)."""
+        post = self.postprocess if postprocess is _OWN else postprocess
+        res = self._predict(image, return_prob)
+        if post is None:
+            return res
+        return (post(res[0]), res[1]) if return_prob else post(res)
+
+    def _predict(self, image, return_prob: bool):
         self.model.eval()
         dev = self._device()
         kind = _output_kind(self.model, self.output)
@@ -416,19 +428,25 @@ class SlidingWindowPredictor:
         return (labels, prob) if return_prob else labels
 
 
-def evaluate_full_res(predictor, pairs: Iterable, num_classes: int = 1, surface=None):
+def evaluate_full_res(predictor, pairs: Iterable, num_classes: int = 1, surface=None, postprocess=None):
     """(Dice, IoU) of full-resolution hard predictions over ``pairs`` = (image, label map) items.
     Binary (num_classes = 1; a pixel is foreground where the map is > 0.5): the reference's
     batch-flattened formulas (cswin:692-708) per image, averaged over the images.  Multi-class: the
     per-class sums of all images, Dice and IoU as the macro means over the classes that occur
     (csu.train._epoch_means).  ``surface``: a csu.metrics.SurfaceMetrics accumulator; every
     (prediction, label map) pair is also fed to it (on the prediction's device, without a
-    synchronisation) and the result is (Dice, IoU, surface.compute())."""
+    synchronisation) and the result is (Dice, IoU, surface.compute()).  ``postprocess``: a
+    csu.components.PostProcess (or any callable on a label map) applied to every prediction before it is
+    scored, instead of the predictor's own setting; None leaves the predictor as it is."""
     from .train import _epoch_means
     K = int(num_classes)
     rows = []
     for image, target in pairs:
-        pred = predictor.predict(image)
+        if postprocess is None:
+            pred = predictor.predict(image)
+        else:       # the raw labels of a predictor that has a setting of its own, then this call's rules
+            own = getattr(predictor, "postprocess", None)
+            pred = postprocess(predictor.predict(image) if own is None else predictor.predict(image, postprocess=None))
         t = torch.as_tensor(np.asarray(target) if not isinstance(target, torch.Tensor) else target).to(pred.device)
         t = t.reshape(pred.shape)
         if surface is not None:

@@ -972,6 +972,54 @@ int csu_edt(int B, int H, int W, int dtype, const void* mask, double sy, double 
             float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Connected-component labelling and the component rules of segmentation post-processing
+ * (csrc/components.hip); the reference has no counterpart.
+ *   labels: a label map (B, H, W), contiguous, CSU_SURFACE_U8 or CSU_SURFACE_I64, read in place.  Value 0 is
+ *   background.  Two neighbouring pixels belong to one component iff they hold the same value and are
+ *   adjacent: `connectivity` CSU_CC_4 (edges) or CSU_CC_8 (edges and corners) for the non-zero values,
+ *   always 4-adjacency for value 0 (the background components come out of the same pass, in
+ *   scipy.ndimage.binary_fill_holes' convention).  All values are labelled in one pass.
+ * csu_ccl: each output may be NULL, not all three.
+ *      comp  int32 (B, H, W): 0 at the zero pixels, elsewhere the component's number within its image,
+ *            1 .. N in raster order of the components' first pixels (for a binary map: scipy.ndimage.label with
+ *            the 3 x 3 all-ones structure for CSU_CC_8, the cross for CSU_CC_4).
+ *      area  int32 (B, H, W): every pixel, the zero ones included, holds the pixel count of its component.
+ *      count int32 (B): N, the number of non-zero components of each image.
+ *      Workspace: csu_ccl_workspace(B, H, W) bytes = 3 x 4 B H W + 4 B ceil(H W / 4096), each of the four
+ *      parts rounded up to 256: parents, {count, non-zero bit, touches-the-border bit} per root, numbers,
+ *      and the root counts of 4096-pixel chunks.  The touches-border field stays in the workspace.
+ * csu_cc_filter: out (B, H, W) of the labels' dtype = the map after three steps, each applied to the map the
+ *      step before produced.  out may be the very buffer of labels (no other overlap).
+ *      1. fill_holes != 0: a hole is a zero component that does not touch the image border, of at most
+ *         max_hole_size pixels (-1: any size); it takes the value of the pixel left of its first pixel in
+ *         raster order, unless that value is >= num_classes (then it stays).
+ *      2. every component of a class c with fewer than min_size[c] pixels becomes 0 (min_size NULL: none).
+ *      3. for every class c with bit c of keep_largest set, all of its components in an image become 0 but
+ *         the largest one; ties go to the lowest component number.
+ *      Classes are the values 1 .. num_classes - 1; min_size has num_classes entries (entry 0 unused).  For
+ *      num_classes = 1 the only class is the value 1 and entry 0 / bit 0 are its rules.  Values >=
+ *      num_classes (an ignore value) form components like any other, are never holes, and no rule touches
+ *      them.  Steps 2 and 3 work on a fresh labelling of the filled map: filling can join components.
+ *      Workspace: csu_cc_filter_workspace(B, H, W) bytes = 2 x 4 B H W + 256 B, each of the three parts
+ *      rounded up to 256: parents, per-root fields, and a 64-bit (area, ~first pixel) key per image and class.
+ * Results are unique by definition (roots are minimum pixel indices, numbers are ranks): bitwise repeatable,
+ * independent of B and of any chunking.  Integer atomics only.  Both take the stream and are capturable
+ * (no allocation, no synchronisation, nothing returned to the host); no workgroup waits for another.
+ * CSU_E_ARG: a size < 1, H or W > 32767, B > 65535 or B ceil(H / 64) ceil(W / 64) > 2^23 (the grid of the tile
+ *      pass), a connectivity other than 4 or 8, an unknown dtype, num_classes outside 1..32, a negative min_size,
+ *      max_hole_size < -1, null labels / workspace / out, all of comp, area, count null.
+ *      CSU_E_WORKSPACE: workspace too small.
+ * ------------------------------------------------------------------------------------- */
+enum csu_cc_connectivity { CSU_CC_4 = 4, CSU_CC_8 = 8 };
+size_t csu_ccl_workspace(int B, int H, int W);
+int csu_ccl(int B, int H, int W, int dtype, const void* labels, int connectivity, void* workspace, size_t ws_bytes,
+            int* comp, int* area, int* count, void* stream);
+size_t csu_cc_filter_workspace(int B, int H, int W);
+int csu_cc_filter(int B, int H, int W, int dtype, const void* labels, int connectivity, int num_classes,
+                  const int* min_size, unsigned keep_largest, int fill_holes, int max_hole_size, void* workspace,
+                  size_t ws_bytes, void* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plain-UNet BatchNorm2d (+ ReLU) and MaxPool2d(2) on NHWC rows (DoubleConv / Down,
  * train_unet_segmentation.py unet:177-204; replaces F.batch_norm + F.relu + F.max_pool2d there).
  * x, y: M = B*H*W rows of C channels (C % 8 == 0), dtype bf16 or f32 (y and dx in x's dtype).
