@@ -20,6 +20,7 @@ from .metrics import (SurfaceMetrics, distance_transform_edt, reference_distance
                       reference_surface_metrics, surface_metrics)
 from .components import (PostProcess, connected_components, postprocess_labels, reference_connected_components,
                          reference_postprocess_labels)
+from .augment import SpatialAugment, reference_augment
 from . import rng
 from .rng import manual_seed
 
@@ -31,4 +32,4 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "SlidingWindowPredictor", "reference_predict", "evaluate_full_res", "plan_axis", "plan_tiles", "window_1d",
            "SurfaceMetrics", "surface_metrics", "reference_surface_metrics", "distance_transform_edt",
            "reference_distance_transform_edt", "connected_components", "postprocess_labels", "PostProcess",
-           "reference_connected_components", "reference_postprocess_labels"]
+           "reference_connected_components", "reference_postprocess_labels", "SpatialAugment", "reference_augment"]

@@ -74,6 +74,15 @@ class HeadFold(ctypes.Structure):
                 ("db_out", c_void_p), ("dw_h", c_void_p)]
 
 
+class AugmentConfig(ctypes.Structure):
+    """csu_augment_config (include/csu.h)."""
+    _fields_ = [(n, c_float) for n in ("p_hflip", "p_vflip", "p_rot90", "p_rotate", "rotate_lo", "rotate_hi", "p_scale",
+                                       "scale_lo", "scale_hi", "p_translate", "translate_x", "translate_y", "p_contrast",
+                                       "contrast_lo", "contrast_hi", "p_brightness", "brightness_lo", "brightness_hi",
+                                       "p_gamma", "gamma_lo", "gamma_hi", "p_noise", "noise_lo", "noise_hi", "p_elastic",
+                                       "elastic_lo", "elastic_hi")] + [("spacing", c_int32)]
+
+
 class ConvGeom(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("B", "H", "W", "C", "OH", "OW", "N", "KH", "KW", "stride", "pad")]
 
@@ -210,6 +219,14 @@ _SIGS = {
     "csu_linear_wgrad_group": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "csu_augment_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "csu_augment_draw": (ctypes.c_int, [ctypes.POINTER(AugmentConfig)] + [ctypes.c_int] * 3 + [c_void_p, ctypes.c_uint,
+                                                                                                ctypes.c_uint, c_void_p,
+                                                                                                c_void_p, c_void_p]),
+    "csu_augment_mean": (ctypes.c_int, [ctypes.c_int, ctypes.c_long] + [c_void_p] * 4),
+    "csu_augment_warp": (ctypes.c_int, [ctypes.c_int] * 3 + [c_void_p] * 4 + [ctypes.c_int, c_void_p, c_void_p,
+                                                                             ctypes.c_uint, ctypes.c_int, c_float,
+                                                                             ctypes.c_int, ctypes.c_int, c_void_p, c_void_p,
+                                                                             c_void_p]),
     "csu_tile_gather": (ctypes.c_int, [ctypes.c_int] * 5 + [c_void_p] * 4),
     "csu_tile_blend": (ctypes.c_int, [ctypes.c_int] * 7 + [c_void_p] + [ctypes.c_long] * 3 + [ctypes.c_int]
                        + [c_void_p] * 3 + [ctypes.c_int] * 4 + [c_void_p]),

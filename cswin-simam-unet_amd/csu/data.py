@@ -179,15 +179,21 @@ class SegmentationDataset(torch.utils.data.Dataset):
     (a palette or greyscale image; a lossless ``<name>.png`` beside the image's name is preferred to
     the same-named file).  Its raw values are resized nearest-neighbour, augmented nearest-neighbour,
     and returned as an int64 (H, W) label map for csu.losses.MultiClassSegLoss.  The device
-    augmentation interpolates masks, so ``device_augment=True`` is refused with it."""
+    augmentation interpolates masks, so ``device_augment=True`` is refused with it.
 
-    def __init__(self, image_dir, mask_dir, image_size=(224, 224), augment=False, device_augment=False, label_mode=False):
+    ``raw=True`` (either mode): ``load()``'s resized uint8 (H, W, 3) image and uint8 (H, W) mask / label map
+    as tensors, not augmented on the host, for ``DeviceAugmentLoader(loader, device, augment=SpatialAugment(...))``
+    (csu.augment), which samples label maps nearest-neighbour.  Label values above 255 raise."""
+
+    def __init__(self, image_dir, mask_dir, image_size=(224, 224), augment=False, device_augment=False, label_mode=False,
+                 raw=False):
         import glob
         import os
         if label_mode and device_augment:
             raise ValueError("SegmentationDataset: label_mode=True cannot be combined with device_augment=True "
                              "(the device augmentation interpolates the mask bilinearly)")
         self.label_mode = bool(label_mode)
+        self.raw = bool(raw)
         self.image_dir, self.mask_dir, self.image_size = image_dir, mask_dir, tuple(image_size)
         self.augment, self.device_augment = augment, device_augment
         self.transform = AugmentationTransform(flip_prob=0.5, rotate_prob=0.25, crop_scale=(0.75, 1.0)) if augment else None
@@ -225,6 +231,13 @@ class SegmentationDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         image, mask = self.load(idx)
+        if self.raw:
+            if mask.dtype != np.uint8:
+                if int(mask.max(initial=0)) > 255 or int(mask.min(initial=0)) < 0:
+                    raise ValueError(f"SegmentationDataset(raw=True): label values outside 0..255 in the mask of "
+                                     f"{self.image_paths[idx]}")
+                mask = mask.astype(np.uint8)
+            return torch.from_numpy(np.ascontiguousarray(image)), torch.from_numpy(np.ascontiguousarray(mask))
         if self.device_augment:
             return torch.from_numpy(np.ascontiguousarray(image)), torch.from_numpy(np.ascontiguousarray(mask))
         if self.transform is not None:
@@ -260,12 +273,21 @@ class DeviceAugmentLoader:
     batches augmented + normalised on ``device`` (one csu_augment_batch launch per batch) in place
     of the reference's per-sample host augmentation inside the DataLoader workers; ``augment=False``
     datasets are only normalised.  Drop-in for ``train_model``'s loaders (images are already on the
-    device there)."""
+    device there).
 
-    def __init__(self, loader, device):
+    ``augment``: a ``csu.augment.SpatialAugment`` applied instead (draw + one csu_augment_warp launch per
+    batch, parameters drawn on the device) over a ``SegmentationDataset(..., raw=True)``; a
+    ``label_mode`` dataset is sampled nearest-neighbour and yields int64 (B, H, W) labels."""
+
+    def __init__(self, loader, device, augment=None):
         self.loader, self.device = loader, torch.device(device)
         ds = loader.dataset
-        self.aug = DeviceAugment(ds.transform if getattr(ds, "augment", False) else None)
+        if augment is None:
+            self.aug = DeviceAugment(ds.transform if getattr(ds, "augment", False) else None)
+        elif getattr(ds, "label_mode", False):
+            self.aug = lambda images, masks: augment(images, masks, mask_mode="nearest", out="labels")
+        else:
+            self.aug = augment
         self.sampler = getattr(loader, "sampler", None)
 
     def __len__(self):

@@ -1590,6 +1590,99 @@ def augment_batch(images: torch.Tensor, masks: torch.Tensor, params) -> Tuple[to
     return out, om
 
 
+AUGMENT_P = 20                                   # CSU_AUGMENT_P: floats per row of the parameter table
+AUGMENT_BORDERS = {"constant": 0, "replicate": 1}
+AUGMENT_MASK_MODES = {("bilinear", "binary"): 0, ("nearest", "binary"): 1, ("nearest", "labels"): 2}
+
+
+def augment_draw(cfg: "_lib.AugmentConfig", B: int, H: int, W: int, snap: torch.Tensor, elastic: bool = False,
+                 site: Optional[int] = None, site_ctrl: Optional[int] = None):
+    """csu_augment_draw: (table fp32 (B, AUGMENT_P), ctrl fp32 (B, 2, Gy, Gx) or None) drawn on the device from
+    the [seed, counter] snapshot `snap`; nothing crosses to the host."""
+    from . import rng
+    from .augment import control_grid
+    require_device(snap)
+    if snap.dtype != torch.int64 or snap.numel() != 2:
+        raise ValueError("augment_draw: snap is an int64 [seed, counter] snapshot (csu.rng)")
+    B, H, W = int(B), int(H), int(W)
+    site = rng.SITE_AUGMENT_DRAW if site is None else int(site)
+    site_ctrl = rng.SITE_AUGMENT_CTRL if site_ctrl is None else int(site_ctrl)
+    table = torch.empty(B, AUGMENT_P, dtype=torch.float32, device=snap.device)
+    ctrl = None
+    if elastic:
+        if int(cfg.spacing) < 4:
+            raise ValueError("augment_draw: elastic control-grid spacing must be >= 4 pixels")
+        ctrl = torch.empty((B, 2) + control_grid(H, W, int(cfg.spacing)), dtype=torch.float32, device=snap.device)
+    _launch("augment_draw", lambda: lib().csu_augment_draw(ctypes.byref(cfg), B, H, W, ptr(snap), site, site_ctrl,
+                                                           ptr(table), ptr(ctrl), stream_ptr(snap.device)),
+            0, 4 * (table.numel() + (ctrl.numel() if ctrl is not None else 0)), prec="f32")
+    return table, ctrl
+
+
+def augment_mean(images: torch.Tensor) -> torch.Tensor:
+    """csu_augment_mean: fp32 (B,) mean of every uint8 image / 255, from an exact integer sum."""
+    require_device(images)
+    if images.dtype != torch.uint8 or images.dim() < 2:
+        raise ValueError("augment_mean: uint8 images (B, ...)")
+    img = images.contiguous()
+    B, n = img.shape[0], img[0].numel()
+    sums = torch.empty(B, dtype=torch.int64, device=img.device)
+    mean = torch.empty(B, dtype=torch.float32, device=img.device)
+    _launch("augment_mean", lambda: lib().csu_augment_mean(B, n, ptr(img), ptr(sums), ptr(mean), stream_ptr(img.device)),
+            0, B * n + 12 * B, prec="f32")
+    return mean
+
+
+def augment_warp(images: torch.Tensor, masks: torch.Tensor, table: torch.Tensor, ctrl: Optional[torch.Tensor] = None,
+                 spacing: int = 0, mean: Optional[torch.Tensor] = None, snap: Optional[torch.Tensor] = None,
+                 border: str = "constant", image_fill: float = 0.0, pad_label: int = 0, mask_mode: str = "bilinear",
+                 out: str = "binary", noise_site: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """csu_augment_warp: uint8 images (B, H, W, 3) and masks (B, H, W) warped through the table's inverse affine
+    and the B-spline field of `ctrl`, images then through the table's intensity steps -> fp32 (B, 3, H, W) and
+    the mask as fp32 (B, 1, H, W) (out="binary") or int64 (B, H, W) (mask_mode="nearest", out="labels").
+    mean: csu_augment_mean's (computed here when None); snap: the snapshot of the noise (None: no noise)."""
+    from . import rng
+    from .augment import control_grid
+    require_device(images, masks, table, ctrl, mean, snap)
+    if images.dtype != torch.uint8 or masks.dtype != torch.uint8:
+        raise ValueError("augment_warp: uint8 images and masks")
+    if images.dim() != 4 or images.shape[3] != 3 or tuple(masks.shape) != tuple(images.shape[:3]):
+        raise ValueError("augment_warp: images (B, H, W, 3) and masks (B, H, W)")
+    B, H, W = images.shape[:3]
+    if table.dtype != torch.float32 or tuple(table.shape) != (B, AUGMENT_P):
+        raise ValueError(f"augment_warp: table is fp32 (B, {AUGMENT_P})")
+    if border not in AUGMENT_BORDERS or (mask_mode, out) not in AUGMENT_MASK_MODES:
+        raise ValueError("augment_warp: border constant / replicate; mask_mode bilinear / nearest; out binary, or labels "
+                         "with nearest")
+    if not 0 <= int(pad_label) <= 255 and out != "labels":
+        raise ValueError("augment_warp: pad_label outside 0..255 needs out='labels'")
+    if ctrl is not None:
+        spacing = int(spacing)
+        if spacing < 4 or ctrl.dtype != torch.float32 or tuple(ctrl.shape) != (B, 2) + control_grid(H, W, spacing):
+            raise ValueError("augment_warp: ctrl is fp32 (B, 2, ceil(H / spacing) + 3, ceil(W / spacing) + 3), spacing >= 4")
+        ctrl = ctrl.contiguous()
+    if snap is not None and (snap.dtype != torch.int64 or snap.numel() != 2):
+        raise ValueError("augment_warp: snap is an int64 [seed, counter] snapshot (csu.rng)")
+    img, msk, tab = images.contiguous(), masks.contiguous(), table.contiguous()
+    if mean is None:
+        mean = augment_mean(img)
+    elif mean.dtype != torch.float32 or tuple(mean.shape) != (B,) or not mean.is_contiguous():
+        raise ValueError("augment_warp: mean is a contiguous fp32 (B,)")
+    mode = AUGMENT_MASK_MODES[(mask_mode, out)]
+    oimg = torch.empty(B, 3, H, W, dtype=torch.float32, device=img.device)
+    if out == "labels":
+        om = torch.empty(B, H, W, dtype=torch.int64, device=img.device)
+    else:
+        om = torch.empty(B, 1, H, W, dtype=torch.float32, device=img.device)
+    site = rng.SITE_AUGMENT_NOISE if noise_site is None else int(noise_site)
+    _launch("augment_warp", lambda: lib().csu_augment_warp(B, H, W, ptr(img), ptr(msk), ptr(tab), ptr(ctrl), int(spacing),
+                                                           ptr(mean), ptr(snap), site, AUGMENT_BORDERS[border],
+                                                           float(image_fill), int(pad_label), mode, ptr(oimg), ptr(om),
+                                                           stream_ptr(img.device)),
+            0, B * H * W * (4 + 12 + om.element_size()), prec="f32")
+    return oimg, om
+
+
 def shared_cast(x: torch.Tensor, dtype: torch.dtype):
     """(xc, xc) -- the same `dtype` copy of x for two consumers (see _SharedCastFn)."""
     return _SharedCastFn.apply(x, dtype)

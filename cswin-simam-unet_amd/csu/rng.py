@@ -34,6 +34,11 @@ OFF_MLP_HIDDEN = 2
 OFF_MLP_OUT = 3
 OFF_DROPPATH_ATTN = 4
 OFF_DROPPATH_MLP = 5
+# csu.augment (csrc/augment_warp.hip): above every CSWinBlock site (the deepest model has fewer than 100 blocks,
+# i.e. sites below 1 + 8 * 100) and below 4096 (the site shares a counter word with bits 32.. of the element index)
+SITE_AUGMENT_DRAW = 4080      # the per-image parameter table
+SITE_AUGMENT_CTRL = 4081      # the elastic control displacements
+SITE_AUGMENT_NOISE = 4082     # the per-pixel Gaussian noise
 
 
 def _dev(device) -> torch.device:

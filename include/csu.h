@@ -890,6 +890,78 @@ int csu_augment_batch(int B, int S, const void* img, const void* mask, const int
                       float* out_mask, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Affine + elastic + intensity augmentation with device-drawn parameters (csrc/augment_warp.hip).
+ * The reference has no counterpart (its augmentation is csu_augment_batch above); this is the
+ * TransUNet / nnU-Net style set, for images, binary masks and label maps, H x W independent.
+ *
+ * The per-image parameter table is float table[B][CSU_AUGMENT_P]:
+ *   [0] hflip (0/1)   [1] vflip (0/1)   [2] clockwise quarter turns k (0..3)
+ *   [3] angle (rad, positive turns the content clockwise on screen: x right, y down)
+ *   [4] scale   [5] tx   [6] ty (pixels)
+ *   [7] contrast   [8] brightness   [9] gamma   [10] noise sigma   [11] elastic magnitude (pixels)
+ *   [12..17] A = {a00, a01, a02, a10, a11, a12}: the folded INVERSE affine; the source position of the
+ *            output pixel centre (x, y) is (a00 x + a01 y + a02, a10 x + a11 y + a12) in pixel-centre
+ *            coordinates.  The content transform is T(t) C R(angle) S(scale) Q(k) F(h, v) C^-1 about
+ *            c = ((W - 1) / 2, (H - 1) / 2), so A = C F Q(k)^T R(angle)^T / scale C^-1 T(-t); composed in
+ *            fp64 and rounded once: exact for angle = 0, scale = 1 and integer t.
+ *   [18..19] reserved (0).
+ * The identity values are 0 (flips, k, angle, t, sigma, magnitude) and 1 (scale, contrast, brightness,
+ * gamma); the kernels read only [7..17] and skip an intensity step whose parameter is its identity.
+ *
+ * csu_augment_draw fills the table, and ctrl when it is not NULL, from the [seed, counter] snapshot
+ * `rng` (device uint64 x 2, csu_rng_advance): row b is a pure function of (seed, counter, site, b),
+ * H, W and cfg -- not of B or the launch shape.  Philox4x32-7 (csrc/rng.hpp), counter words
+ * {j, (b << 12) ^ site, counter}; uniforms are (bits >> 8) / 2^24.  Each transform is applied when its
+ * uniform is below its probability and keeps its identity value otherwise; a quarter turn that is
+ * applied is 1, 2 or 3; scale is log-uniform, everything else uniform in [lo, hi]; tx in
+ * [-translate_x, translate_x].  ctrl: float [B][2][Gy][Gx] (x displacements, then y), Gx =
+ * ceil(W / spacing) + 3, Gy = ceil(H / spacing) + 3, uniform in [-1, 1) * table[b][11], drawn under
+ * site_ctrl.  Limits of the three calls: B <= 2^20 (csu_augment_mean: 65535), H W < 2^31, H <= 262140, sites
+ * below 4096, spacing >= 4 when ctrl is given.
+ *
+ * csu_augment_mean: mean[b] = the mean of image b's n bytes / 255 from an exact 64-bit integer sum
+ * (`sums`, B uint64 of scratch, zeroed by the call), so it does not depend on the order of the adds.
+ *
+ * csu_augment_warp: one pass over the output pixels.  img uint8 (B, H, W, 3), mask uint8 (B, H, W).
+ *   position: (x, y) is displaced by the uniform cubic B-spline of ctrl (NULL or magnitude 0: none):
+ *     i = x / spacing, f = (x mod spacing) / spacing, d = c00 + sum_ab B_a(f_y) B_b(f_x) (c_ab - c00)
+ *     over the 4 x 4 control points from (i_y, i_x) (relative to the first one, so that a constant field
+ *     is reproduced exactly), then mapped through A.
+ *   border CSU_AUG_CONSTANT: image taps outside read image_fill (in output units, [0, 1]), bilinear mask
+ *     taps outside read 0, a nearest mask value outside is pad_label.  CSU_AUG_REPLICATE: the source
+ *     coordinate is clamped to the image for all three.
+ *   image: bilinear sample, then per channel v = s / 255; v = (v - mean) contrast + mean; v *= brightness;
+ *     clamp to [0, 1]; v = v^gamma; v += sigma n; clamp.  n is a standard normal (Box-Muller) of the Philox
+ *     call {y W + x, (b << 12) ^ noise_site, counter}: channels 0 / 1 take the cosine / sine branch of its
+ *     first pair of words, channel 2 the cosine branch of the second.  rng NULL: no noise.
+ *     out_img fp32 (B, 3, H, W).
+ *   mask_mode CSU_AUG_MASK_BILINEAR: out_mask fp32 (B, 1, H, W) = bilinear sample / 255, not rounded.
+ *     CSU_AUG_MASK_NEAREST: the value at (floor(sx + 0.5), floor(sy + 0.5)) / 255 as fp32 (B, 1, H, W).
+ *     CSU_AUG_MASK_LABELS: that value as int64 (B, H, W) (pad_label may be an ignore index such as 255).
+ * ------------------------------------------------------------------------------------- */
+#define CSU_AUGMENT_P 20
+enum csu_augment_border { CSU_AUG_CONSTANT = 0, CSU_AUG_REPLICATE = 1 };
+enum csu_augment_mask_mode { CSU_AUG_MASK_BILINEAR = 0, CSU_AUG_MASK_NEAREST = 1, CSU_AUG_MASK_LABELS = 2 };
+typedef struct {
+    float p_hflip, p_vflip, p_rot90;
+    float p_rotate, rotate_lo, rotate_hi;          /* radians */
+    float p_scale, scale_lo, scale_hi;             /* > 0 */
+    float p_translate, translate_x, translate_y;   /* largest |shift| in pixels */
+    float p_contrast, contrast_lo, contrast_hi;
+    float p_brightness, brightness_lo, brightness_hi;
+    float p_gamma, gamma_lo, gamma_hi;             /* > 0 */
+    float p_noise, noise_lo, noise_hi;             /* sigma, >= 0 */
+    float p_elastic, elastic_lo, elastic_hi;       /* magnitude in pixels, >= 0 */
+    int32_t spacing;                               /* control-grid spacing in pixels (ctrl != NULL) */
+} csu_augment_config;
+int csu_augment_draw(const csu_augment_config* cfg, int B, int H, int W, const uint64_t* rng, unsigned site,
+                     unsigned site_ctrl, float* table, float* ctrl, void* stream);
+int csu_augment_mean(int B, long n, const void* img, uint64_t* sums, float* mean, void* stream);
+int csu_augment_warp(int B, int H, int W, const void* img, const void* mask, const float* table, const float* ctrl,
+                     int spacing, const float* mean, const uint64_t* rng, unsigned noise_site, int border,
+                     float image_fill, int pad_label, int mask_mode, float* out_img, void* out_mask, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Tiled whole-image inference (csrc/tile.hip): sliding-window prediction of an H x W image with a
  * network of fixed S x S input, with test-time augmentation.  The reference has no counterpart.
  *   table: int32 (B, 6) on the device, one record per batch slot: {y0, x0, hflip, vflip, clockwise
