@@ -31,6 +31,10 @@
 //              class, V-wide loads on units that lie inside the chunk on a vector boundary; the
 //              first / last unit of a chunk that starts off a boundary are read per element.
 //   strided    anything else (dense class-last with K != KB): per-element loads.
+// Boundary term (csu_seg_bd_*, template flag BD; off in csu_seg_ce_*, whose arithmetic it leaves alone):
+//   + w_bd[0] BD,  BD = sum over live pixels and c in Cb of p_c phi_c / (n |Cb|),  n = sum_c T_c,  Cb = 1 .. K-1 or all;
+//   phi dense fp32 (B, K, HW) read per class plane; one more partial sum per item (index 2 + 5 K); ce_finish leaves
+//   1 / (n |Cb|) behind 1 / sum w; backward adds g w_bd / (n |Cb|) p_k (phi_k [k in Cb] - sum_{c in Cb} phi_c p_c).
 // No label ever indexes memory (class weight and z_t are selected by comparison), so a label
 // outside [0, K) cannot fault; it matches no class.  The summation order is a function of the
 // shape, the strides and the address mod 16 only.
@@ -73,6 +77,14 @@ struct CeArgs {
     const float* cw;
 };
 
+// The boundary term (csu_seg_bd_*): BD = sum over live pixels and c in Cb of p_c phi_c / (n |Cb|), n = the live
+// pixels whose label is a class, Cb = classes 1 .. K-1 or all of them (bg).  phi is dense fp32 (B, K, HW).
+struct BdArgs {
+    const float* phi;
+    const float* w_bd;   // one float on the device
+    int bg;
+};
+
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -102,6 +114,31 @@ template <int V, typename T> __device__ __forceinline__ void storev(T* p, const 
 }
 // widest access of a class-last pixel's KB elements: 16 B, or all of it when that is less
 template <typename T, int KB> constexpr int cl_vec() { return KB * (int)sizeof(T) >= 16 ? 16 / (int)sizeof(T) : KB; }
+
+// f[j][k] = phi of pixel e0 + j and class k for the classes that carry the term, else 0; only pixels inside
+// [lo, hi) are read.  A unit that is whole and whose plane address is on a vector boundary takes one V-wide load.
+template <int KB, int V>
+__device__ __forceinline__ void load_phi(const CeArgs& a, const BdArgs& bd, long b, long e0, long lo, long hi, bool full,
+                                         float (&f)[V][KB]) {
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) f[j][k] = 0.f;
+        if (k < a.K && (bd.bg || k > 0)) {
+            const float* q = bd.phi + (b * a.K + k) * a.HW + e0;
+            if (V > 1 && full && ((uintptr_t)q % (V * sizeof(float))) == 0) {
+                float v[V];
+                loadv<V>(q, v);
+#pragma unroll
+                for (int j = 0; j < V; ++j) f[j][k] = v[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j)
+                    if (e0 + j >= lo && e0 + j < hi) f[j][k] = q[j];
+            }
+        }
+    }
+}
 
 // One unit = V pixels e0 .. e0 + V - 1 of image base zb; pixels outside [lo, hi) are dead.
 // z[j][k] = logit of pixel j, class k; 0 for a dead pixel, -inf for k >= K.
@@ -193,13 +230,14 @@ __device__ __forceinline__ void item_range(const CeArgs& a, long it, bool vec_ok
     nu = (hi - e_first + V - 1) / V;
 }
 
-template <typename T, int KB, int MODE>
-__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __restrict__ partial) {
+// BD: one more sum per item, the boundary term's sum of p_c phi_c, at index 2 + 5 K
+template <typename T, int KB, int MODE, bool BD>
+__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, int vec_ok, float* __restrict__ partial) {
     constexpr int V = ce_vec(KB, MODE);
     constexpr bool LANE_CNT = KB >= 16;
     constexpr int NC = LANE_CNT ? 1 : KB;
-    __shared__ float red[NT / 64][2 + 5 * KB];
-    const int K = a.K, ns = 2 + 5 * K;
+    __shared__ float red[NT / 64][2 + 5 * KB + (BD ? 1 : 0)];
+    const int K = a.K, ns = 2 + 5 * K + (BD ? 1 : 0);
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float cw[KB];
 #pragma unroll
@@ -208,7 +246,7 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __
         long b, lo, hi, e_first, nu;
         item_range<T, V>(a, it, vec_ok, b, lo, hi, e_first, nu);
         const T* zb = (const T*)a.z + b * a.s_b;
-        float ce = 0.f, sw = 0.f, tp[KB], ps[KB];
+        float ce = 0.f, sw = 0.f, bsum = 0.f, tp[KB], ps[KB];
         // counts: wave-uniform ballot sums, one scalar per class (small buckets) or held by lane k for
         // class k (KB >= 16: 3 registers instead of 3 KB)
         int ct[NC], ci[NC], cp[NC];
@@ -226,6 +264,8 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __
             const bool full = vec_ok && e0 >= lo && e0 + V <= hi;
             float z[V][KB];
             load_unit<T, KB, MODE, V>(a, zb, e0, lo, hi, full, z);
+            float f[BD ? V : 1][BD ? KB : 1];
+            if constexpr (BD) load_phi<KB, V>(a, bd, b, e0, lo, hi, e0 >= lo && e0 + V <= hi, f);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 bool live;
@@ -251,6 +291,12 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __
                     count(cp, k, pred == k);
                     count(ci, k, pred == k && t == k);
                 }
+                if constexpr (BD) {
+                    float pf = 0.f;
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) pf = __builtin_fmaf(z[j][k], f[j][k], pf);
+                    bsum += live ? pf : 0.f;
+                }
             }
         }
         ce = wave_sum(ce);
@@ -258,6 +304,10 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __
         if (lane == 0) {
             red[wv][0] = ce;
             red[wv][1] = sw;
+        }
+        if constexpr (BD) {
+            bsum = wave_sum(bsum);
+            if (lane == 0) red[wv][2 + 5 * K] = bsum;
         }
 #pragma unroll
         for (int k = 0; k < KB; ++k) {
@@ -286,14 +336,16 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, int vec_ok, float* __
     }
 }
 
-// coef: rows x K x 2 floats (A, C), then 1 / sum w
+// coef: rows x K x 2 floats (A, C), then 1 / sum w; BD: then 1 / (n |Cb|), and terms = {the loss without the
+// boundary term, BD}
+template <bool BD>
 __global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows, const float* __restrict__ partial,
                                                 float w_ce, float w_tv, float alpha, float beta, float smooth, int bg,
-                                                float* __restrict__ loss, double* __restrict__ stats,
-                                                float* __restrict__ coef) {
-    __shared__ double red[3][NT / 64];
+                                                BdArgs bd, float* __restrict__ terms, float* __restrict__ loss,
+                                                double* __restrict__ stats, float* __restrict__ coef) {
+    __shared__ double red[BD ? 5 : 3][NT / 64];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int ns = 2 + 5 * K;
+    const int ns = 2 + 5 * K + (BD ? 1 : 0);
     const long items = (long)B * cpi;
     const long ipr = rows == 1 ? items : cpi;   // items per row
     const double a = alpha, b = beta, g = 1.0 - a - b, sm = smooth;
@@ -349,25 +401,60 @@ __global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows,
         red[1][w] = ce;
         red[2][w] = sw;
     }
+    if constexpr (BD) {
+        double n = 0., bs = 0.;   // n: the counts T_c of every class and item (integers: exact in any order)
+        for (long i = threadIdx.x; i < items; i += NT) {
+            const float* q = partial + i * ns + 2 + 2 * K;
+            for (int c = 0; c < K; ++c) n += (double)q[c];
+            bs += (double)partial[i * ns + 2 + 5 * K];
+        }
+        n = wave_sum_d(n);
+        bs = wave_sum_d(bs);
+        if (lane == 0) {
+            red[3][w] = n;
+            red[4][w] = bs;
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double tot[3];
+        double tot[BD ? 5 : 3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) tot[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+        for (int k = 0; k < (BD ? 5 : 3); ++k) tot[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
         const double isw = tot[2] > 0. ? 1.0 / tot[2] : 0.;
         const int nc = bg ? K : K - 1;
-        loss[0] = (float)((double)w_ce * tot[1] * isw + (double)w_tv * tot[0] / ((double)rows * nc));
+        const double base = (double)w_ce * tot[1] * isw + (double)w_tv * tot[0] / ((double)rows * nc);
         coef[2 * (long)rows * K] = (float)isw;
+        if constexpr (BD) {
+            const double inb = tot[3] > 0. ? 1.0 / (tot[3] * (double)(bd.bg ? K : K - 1)) : 0.;
+            const double term = tot[4] * inb;
+            terms[0] = (float)base;
+            terms[1] = (float)term;
+            loss[0] = (float)(base + (double)bd.w_bd[0] * term);
+            coef[2 * (long)rows * K + 1] = (float)inb;
+        } else {
+            loss[0] = (float)base;
+        }
     }
 }
 
-template <typename T, int KB, int MODE>
-__global__ __launch_bounds__(NT) void ce_backward(CeArgs a, int vec_ok, int rows, const float* __restrict__ dloss,
+// BD: dz_k += g w_bd / (n |Cb|) p_k (f_k - sum_c f_c p_c), f = phi on the classes that carry the term
+// csu_seg_bd_bwd launches both instantiations with bd.w_bd set and exactly one of them works: the one without the
+// term when it is switched off (w_bd[0] = 0, or a zero upstream gradient), so that phi is not read and the
+// gradient is csu_seg_ce_bwd's bit for bit.  One kernel with the term in the same expression does not give that:
+// the compiler contracts and packs the multiplies and adds of the whole expression as it sees fit.
+template <typename T, int KB, int MODE, bool BD>
+__global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, int vec_ok, int rows, const float* __restrict__ dloss,
                                                   const float* __restrict__ coef, float w_ce, float tv_scale,
                                                   T* __restrict__ dz) {
     constexpr int V = ce_vec(KB, MODE);
     const int K = a.K;
+    if (bd.w_bd != nullptr) {
+        const bool off = dloss[0] * bd.w_bd[0] * coef[2 * (long)rows * K + 1] == 0.f;
+        if (off == BD) return;
+    }
     const float g = dloss[0], g1 = g * w_ce * coef[2 * (long)rows * K], g2 = g * tv_scale;
+    float g3 = 0.f;
+    if constexpr (BD) g3 = g * bd.w_bd[0] * coef[2 * (long)rows * K + 1];
     float cw[KB];
 #pragma unroll
     for (int k = 0; k < KB; ++k) cw[k] = (a.cw && k < K) ? a.cw[k] : 1.f;
@@ -389,6 +476,8 @@ __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, int vec_ok, int rows
             const bool full = vec_ok && e0 >= lo && e0 + V <= hi;
             float z[V][KB];
             load_unit<T, KB, MODE, V>(a, zb, e0, lo, hi, full, z);
+            float f[BD ? V : 1][BD ? KB : 1];
+            if constexpr (BD) load_phi<KB, V>(a, bd, b, e0, lo, hi, e0 >= lo && e0 + V <= hi, f);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 bool live;
@@ -403,10 +492,16 @@ __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, int vec_ok, int rows
 #pragma unroll
                 for (int k = 0; k < KB; ++k) dot += ((t == k ? A[k] : 0.f) - C[k]) * z[j][k];
                 const float c1 = g1 * wt;
+                float fdot = 0.f;
+                if constexpr (BD) {
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) fdot = __builtin_fmaf(f[j][k], z[j][k], fdot);
+                }
 #pragma unroll
                 for (int k = 0; k < KB; ++k) {
                     const float pk = z[j][k], G = (t == k ? A[k] : 0.f) - C[k];
-                    const float d = c1 * (pk - (t == k ? 1.f : 0.f)) - g2 * pk * (G - dot);
+                    float d = c1 * (pk - (t == k ? 1.f : 0.f)) - g2 * pk * (G - dot);
+                    if constexpr (BD) d = __builtin_fmaf(g3, pk * (f[j][k] - fdot), d);
                     z[j][k] = live ? d : 0.f;
                 }
             }
@@ -484,7 +579,7 @@ template <class F> void with_mode(int mode, F&& f) {
 }
 
 int ce_args(const char* what, int B, int K, long HW, int rows, int dtype, long s_b, long s_k, long s_pix, int label_dtype,
-            float w_ce, float w_tv) {
+            float w_ce, float w_tv, bool both_zero_ok = false) {
     const std::string w(what);
     if (B < 1 || HW < 1) return fail(CSU_E_ARG, w + ": B and HW must be >= 1");
     if (K < 2 || K > KMAX) return fail(CSU_E_ARG, w + ": 2 <= K <= 32 classes (more: the caller's torch composition)");
@@ -493,7 +588,7 @@ int ce_args(const char* what, int B, int K, long HW, int rows, int dtype, long s
     if (label_dtype != 0 && label_dtype != 1) return fail(CSU_E_ARG, w + ": label_dtype must be 0 (uint8) or 1 (int64)");
     if (s_k < 1 || s_pix < 1 || s_b < 0) return fail(CSU_E_ARG, w + ": strides must be positive");
     if (!(w_ce >= 0.f) || !(w_tv >= 0.f)) return fail(CSU_E_ARG, w + ": w_ce and w_tversky must be >= 0");
-    if (w_ce == 0.f && w_tv == 0.f) return fail(CSU_E_ARG, w + ": w_ce and w_tversky are both zero");
+    if (w_ce == 0.f && w_tv == 0.f && !both_zero_ok) return fail(CSU_E_ARG, w + ": w_ce and w_tversky are both zero");
     return 0;
 }
 
@@ -505,6 +600,56 @@ CeArgs ce_pack(int B, int K, long HW, const void* z, long s_b, long s_k, long s_
     a.HW = HW; a.clen = s.clen; a.items = s.items; a.s_b = s_b; a.s_k = s_k; a.s_pix = s_pix; a.ignore = ignore;
     a.z = z; a.t = t; a.cw = cw;
     return a;
+}
+
+// the two forward launches and the backward launch, shared by csu_seg_ce_* (BD = false) and csu_seg_bd_*
+template <bool BD>
+int ce_forward(const char* what, const CeArgs& a, const BdArgs& bd, int rows, int dtype, int pad_ok, float w_ce, float w_tv,
+               float alpha, float beta, float smooth, int include_background, float* terms, float* loss, double* stats,
+               float* coef, void* workspace, void* stream) {
+    const int K = a.K, KB = ce_bucket(K);
+    const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
+    hipStream_t st = as_stream(stream);
+    int vec_ok = 0;
+    const int mode = dtype == CSU_F32 ? ce_mode<float>(K, KB, a.z, nullptr, a.s_b, a.s_k, a.s_pix, pad_ok, &vec_ok)
+                                            : ce_mode<bf16>(K, KB, a.z, nullptr, a.s_b, a.s_k, a.s_pix, pad_ok, &vec_ok);
+    with_flag(dtype == CSU_F32, [&](auto f32) {
+        using T = std::conditional_t<decltype(f32)::value, float, bf16>;
+        with_bucket(KB, [&](auto kb) {
+            with_mode(mode, [&](auto md) {
+                ce_partial<T, decltype(kb)::value, decltype(md)::value, BD><<<nb, NT, 0, st>>>(a, bd, vec_ok, (float*)workspace);
+            });
+        });
+    });
+    if (int e = check_launch(what)) return e;
+    ce_finish<BD><<<1, NT, 0, st>>>(a.B, K, a.cpi, rows, (const float*)workspace, w_ce, w_tv, alpha, beta, smooth,
+                                    include_background != 0, bd, terms, loss, stats, coef);
+    return check_launch(what);
+}
+
+template <bool BD>
+int ce_backward_launch(const char* what, const CeArgs& a, const BdArgs& bd, int rows, int dtype, int pad_ok, float w_ce,
+                       float w_tv, int include_background, const float* dloss, const float* coef, void* dz, void* stream) {
+    const int K = a.K, KB = ce_bucket(K);
+    const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
+    hipStream_t st = as_stream(stream);
+    int vec_ok = 0;
+    const int mode = dtype == CSU_F32 ? ce_mode<float>(K, KB, a.z, dz, a.s_b, a.s_k, a.s_pix, pad_ok, &vec_ok)
+                                            : ce_mode<bf16>(K, KB, a.z, dz, a.s_b, a.s_k, a.s_pix, pad_ok, &vec_ok);
+    const float tv_scale = w_tv / ((float)rows * (float)(include_background ? K : K - 1));
+    with_flag(dtype == CSU_F32, [&](auto f32) {
+        using T = std::conditional_t<decltype(f32)::value, float, bf16>;
+        with_bucket(KB, [&](auto kb) {
+            with_mode(mode, [&](auto md) {
+                if constexpr (BD)   // the gated pair: see ce_backward
+                    ce_backward<T, decltype(kb)::value, decltype(md)::value, false>
+                        <<<nb, NT, 0, st>>>(a, bd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
+                ce_backward<T, decltype(kb)::value, decltype(md)::value, BD>
+                    <<<nb, NT, 0, st>>>(a, bd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
+            });
+        });
+    });
+    return check_launch(what);
 }
 
 }  // namespace
@@ -527,24 +672,8 @@ extern "C" int csu_seg_ce_fwd(int B, int K, long HW, int rows, int dtype, const 
     if (!z || !t || !loss || !coef) return fail(CSU_E_ARG, "seg_ce_fwd: null z, t, loss or coef");
     if (!workspace || ws_bytes < csu_seg_ce_workspace(B, K, HW)) return fail(CSU_E_WORKSPACE, "seg_ce_fwd: workspace");
     const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
-    const int KB = ce_bucket(K);
-    const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
-    hipStream_t st = as_stream(stream);
-    int vec_ok = 0;
-    const int mode = dtype == CSU_F32 ? ce_mode<float>(K, KB, z, nullptr, s_b, s_k, s_pix, pad_ok, &vec_ok)
-                                            : ce_mode<bf16>(K, KB, z, nullptr, s_b, s_k, s_pix, pad_ok, &vec_ok);
-    with_flag(dtype == CSU_F32, [&](auto f32) {
-        using T = std::conditional_t<decltype(f32)::value, float, bf16>;
-        with_bucket(KB, [&](auto kb) {
-            with_mode(mode, [&](auto md) {
-                ce_partial<T, decltype(kb)::value, decltype(md)::value><<<nb, NT, 0, st>>>(a, vec_ok, (float*)workspace);
-            });
-        });
-    });
-    if (int e = check_launch("seg_ce_fwd")) return e;
-    ce_finish<<<1, NT, 0, st>>>(B, K, a.cpi, rows, (const float*)workspace, w_ce, w_tversky, alpha, beta, smooth,
-                                include_background != 0, loss, stats, coef);
-    return check_launch("seg_ce_fwd");
+    return ce_forward<false>("seg_ce_fwd", a, BdArgs{nullptr, nullptr, 0}, rows, dtype, pad_ok, w_ce, w_tversky, alpha, beta,
+                             smooth, include_background, nullptr, loss, stats, coef, workspace, stream);
 }
 
 extern "C" int csu_seg_ce_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
@@ -554,21 +683,40 @@ extern "C" int csu_seg_ce_bwd(int B, int K, long HW, int rows, int dtype, const 
     if (int e = ce_args("seg_ce_bwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky)) return e;
     if (!z || !t || !dloss || !coef || !dz) return fail(CSU_E_ARG, "seg_ce_bwd: null z, t, dloss, coef or dz");
     const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
-    const int KB = ce_bucket(K);
-    const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
-    hipStream_t st = as_stream(stream);
-    int vec_ok = 0;
-    const int mode = dtype == CSU_F32 ? ce_mode<float>(K, KB, z, dz, s_b, s_k, s_pix, pad_ok, &vec_ok)
-                                            : ce_mode<bf16>(K, KB, z, dz, s_b, s_k, s_pix, pad_ok, &vec_ok);
-    const float tv_scale = w_tversky / ((float)rows * (float)(include_background ? K : K - 1));
-    with_flag(dtype == CSU_F32, [&](auto f32) {
-        using T = std::conditional_t<decltype(f32)::value, float, bf16>;
-        with_bucket(KB, [&](auto kb) {
-            with_mode(mode, [&](auto md) {
-                ce_backward<T, decltype(kb)::value, decltype(md)::value>
-                    <<<nb, NT, 0, st>>>(a, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
-            });
-        });
-    });
-    return check_launch("seg_ce_bwd");
+    return ce_backward_launch<false>("seg_ce_bwd", a, BdArgs{nullptr, nullptr, 0}, rows, dtype, pad_ok, w_ce, w_tversky,
+                                     include_background, dloss, coef, dz, stream);
+}
+
+// ---- the same loss with the boundary term: + w_bd[0] BD ---------------------------------------------
+extern "C" size_t csu_seg_bd_workspace(int B, int K, long HW) {
+    if (B < 1 || HW < 1 || K < 2 || K > KMAX) return 0;
+    return (size_t)ce_plan(B, HW).items * (ce_nsum(K) + 1) * sizeof(float);
+}
+
+extern "C" int csu_seg_bd_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                              int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                              float w_ce, float w_tversky, float alpha, float beta, float smooth, int include_background,
+                              const float* phi, const float* w_bd, int bd_background, float* loss, float* terms,
+                              double* stats, float* coef, void* workspace, size_t ws_bytes, void* stream) {
+    if (int e = ce_args("seg_bd_fwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky, true)) return e;
+    if (!(alpha >= 0.f) || !(beta >= 0.f)) return fail(CSU_E_ARG, "seg_bd_fwd: alpha and beta must be >= 0");
+    if (!(smooth > 0.f)) return fail(CSU_E_ARG, "seg_bd_fwd: smooth must be > 0");
+    if (!z || !t || !loss || !coef || !terms) return fail(CSU_E_ARG, "seg_bd_fwd: null z, t, loss, terms or coef");
+    if (!phi || !w_bd) return fail(CSU_E_ARG, "seg_bd_fwd: null phi or w_bd");
+    if (!workspace || ws_bytes < csu_seg_bd_workspace(B, K, HW)) return fail(CSU_E_WORKSPACE, "seg_bd_fwd: workspace");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    return ce_forward<true>("seg_bd_fwd", a, BdArgs{phi, w_bd, bd_background != 0}, rows, dtype, pad_ok, w_ce, w_tversky, alpha,
+                            beta, smooth, include_background, terms, loss, stats, coef, workspace, stream);
+}
+
+extern "C" int csu_seg_bd_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                              int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                              const float* dloss, const float* coef, float w_ce, float w_tversky, int include_background,
+                              const float* phi, const float* w_bd, int bd_background, void* dz, void* stream) {
+    if (int e = ce_args("seg_bd_bwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky, true)) return e;
+    if (!z || !t || !dloss || !coef || !dz) return fail(CSU_E_ARG, "seg_bd_bwd: null z, t, dloss, coef or dz");
+    if (!phi || !w_bd) return fail(CSU_E_ARG, "seg_bd_bwd: null phi or w_bd");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    return ce_backward_launch<true>("seg_bd_bwd", a, BdArgs{phi, w_bd, bd_background != 0}, rows, dtype, pad_ok, w_ce, w_tversky,
+                                    include_background, dloss, coef, dz, stream);
 }

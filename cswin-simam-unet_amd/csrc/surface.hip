@@ -21,6 +21,9 @@
 //            keys that match the prefix so far (integer atomics), the bin picked at the start of the next
 //            launch by every workgroup alike.  Ranks come from the device-side counts.
 //   finish   fp64 (hd, hd95, assd, nsd, |dP|, |dT|) per pair; NaN in the first four where a mask is empty.
+// Signed distance maps (csu_signed_distance, the boundary loss's phi) reuse the column pass with two more site
+// modes -- every pixel on the class, every pixel off it -- as the two fields of a pair, and one row pass that
+// stages the row of both (4 W bytes of LDS) and searches, per pixel, the field of the other side.
 #include <algorithm>
 
 #include "common.hpp"
@@ -30,6 +33,7 @@ namespace {
 
 constexpr int CMAX = 32;
 constexpr int DMAX = 32767;          // H, W: g fits uint16 below NONE, 2 W bytes of LDS fit 64 KiB
+constexpr int SDMAX = 16383;         // signed distance maps: the rows of two fields share the 64 KiB
 constexpr unsigned short NONE = 0xFFFF;
 constexpr unsigned NOKEY_I = 0x7FFFFFFFu;   // no site at all (int path); above every legal 2 * 32766^2
 constexpr int NT = 256;
@@ -37,7 +41,10 @@ constexpr int COLS = 64;             // columns per column-pass workgroup: one w
 constexpr int SEGMAX = 16;           // row segments of a column, one thread each
 constexpr int PASSES = 4, BINS = 256;
 constexpr int HBMAX = 64;            // histogram workgroups per pair
-enum { SITE_CLASS = 0, SITE_BINARY = 1, SITE_ZERO = 2 };
+enum { SITE_CLASS = 0, SITE_BINARY = 1, SITE_ZERO = 2, SITE_EQ = 3, SITE_NE = 4 };
+// SITE_CLASS / SITE_BINARY: the sites are a mask's border pixels; the others take every pixel that is zero, that
+// holds the class (SITE_EQ), or that does not (SITE_NE), as a site
+constexpr bool site_is_border(int mode) { return mode == SITE_CLASS || mode == SITE_BINARY; }
 
 inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
@@ -65,7 +72,7 @@ __global__ __launch_bounds__(COLS* SEGMAX) void column_kernel(int C, int H, int 
     int first = -1, last = -1;
     if (on) {
         bool up = false, cur = false;
-        if (MODE != SITE_ZERO && y0 < y1) {
+        if (site_is_border(MODE) && y0 < y1) {
             up = in_mask<T, MODE>(img, H, W, y0 - 1, x, cls);
             cur = in_mask<T, MODE>(img, H, W, y0, x, cls);
         }
@@ -74,6 +81,8 @@ __global__ __launch_bounds__(COLS* SEGMAX) void column_kernel(int C, int H, int 
             bool site;
             if (MODE == SITE_ZERO) {
                 site = img[(long)y * W + x] == (T)0;
+            } else if (MODE == SITE_EQ || MODE == SITE_NE) {
+                site = ((long)img[(long)y * W + x] == (long)cls) == (MODE == SITE_EQ);
             } else {
                 const bool dn = in_mask<T, MODE>(img, H, W, y + 1, x, cls);
                 const bool lf = in_mask<T, MODE>(img, H, W, y, x - 1, cls), rt = in_mask<T, MODE>(img, H, W, y, x + 1, cls);
@@ -245,6 +254,94 @@ __global__ __launch_bounds__(NT) void row_kernel(RowArgs a) {
             a.pcnt[i] = p.cnt;
             a.ptau[i] = p.tau;
         }
+    }
+}
+
+// ---- signed distance maps ---------------------------------------------------------------------------
+// row_search with the outward walk cut at kmax columns (kmax >= W: no cut).  With a clip the caller passes the
+// first k whose columns lie beyond the clip radius: what the cut leaves out cannot bring the result under it.
+template <bool ISO>
+__device__ __forceinline__ unsigned row_search_cut(const unsigned short* row, int W, int x, int kmax, float sy2, float sx2) {
+    if (ISO) {
+        int best = (int)NOKEY_I;
+        const int g0 = row[x];
+        if (g0 != NONE) best = g0 * g0;
+        for (int k = 1; k < kmax && (x - k >= 0 || x + k < W); ++k) {
+            const int k2 = k * k;
+            if (k2 >= best) break;
+            if (x - k >= 0) {
+                const int gv = row[x - k];
+                if (gv != NONE) best = min(best, gv * gv + k2);
+            }
+            if (x + k < W) {
+                const int gv = row[x + k];
+                if (gv != NONE) best = min(best, gv * gv + k2);
+            }
+        }
+        return (unsigned)best;
+    } else {
+        float best = INFINITY;
+        const int g0 = row[x];
+        if (g0 != NONE) best = sy2 * (float)(g0 * g0);
+        for (int k = 1; k < kmax && (x - k >= 0 || x + k < W); ++k) {
+            const float kk = sx2 * (float)(k * k);
+            if (kk >= best) break;
+            if (x - k >= 0) {
+                const int gv = row[x - k];
+                if (gv != NONE) best = fminf(best, sy2 * (float)(gv * gv) + kk);
+            }
+            if (x + k < W) {
+                const int gv = row[x + k];
+                if (gv != NONE) best = fminf(best, sy2 * (float)(gv * gv) + kk);
+            }
+        }
+        return __float_as_uint(best);
+    }
+}
+
+struct SignedArgs {
+    int H, W, C, out_classes, out_c0, kmax;
+    float sy2, sx2;
+    double s2, step, clip;      // step = min(sy, sx); clip <= 0: none
+    const unsigned short* g;    // (pairs, 2, H, W): field 0 has its sites on the class, field 1 off it
+    float* out;                 // (B, out_classes, H, W)
+};
+
+// grid (H, pairs), NT threads, dynamic LDS 4 W bytes rounded up to 16: the row of both fields.  A pixel on the class
+// (g of field 0 is 0 there) searches field 1, any other pixel field 0.  A field without a site in this row's columns
+// has none at all (g != NONE says "this column has a site"): the class is absent or fills the image, phi = 0.
+template <bool ISO>
+__global__ __launch_bounds__(NT) void signed_row_kernel(SignedArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned short* on = reinterpret_cast<unsigned short*>(smem);
+    const int W = a.W, y = blockIdx.x, pair = blockIdx.y;
+    unsigned short* off = on + ((W + 7) & ~7);
+    const unsigned short* g_on = a.g + (((long)pair * 2) * a.H + y) * W;
+    const unsigned short* g_off = a.g + (((long)pair * 2 + 1) * a.H + y) * W;
+    int any = 0;
+    for (int x = threadIdx.x; x < W; x += NT) {
+        const unsigned short u = g_on[x], v = g_off[x];
+        on[x] = u;
+        off[x] = v;
+        any |= (u != NONE ? 1 : 0) | (v != NONE ? 2 : 0);
+    }
+    const int any_on = __syncthreads_or(any & 1), any_off = __syncthreads_or(any & 2);
+    const bool both = any_on && any_off;
+    const int b = pair / a.C, c = pair % a.C;
+    float* o = a.out + (((long)b * a.out_classes + a.out_c0 + c) * a.H + y) * W;
+    const unsigned step_key = __float_as_uint(fminf(a.sy2, a.sx2));
+    for (int x = threadIdx.x; x < W; x += NT) {
+        double phi = 0.0;
+        if (both) {
+            const bool inside = on[x] == 0;
+            const unsigned key = row_search_cut<ISO>(inside ? off : on, W, x, a.kmax, a.sy2, a.sx2);
+            const double d = key_dist<ISO>(key, a.s2);
+            // the fp32 path: one step along the finer axis is the distance `step` itself, so that an inner border
+            // pixel is 0 and not the rounding of sqrt(fp32(step^2)) - step
+            phi = !inside ? d : (!ISO && key == step_key) ? 0.0 : a.step - d;
+            if (a.clip > 0.0) phi = fmin(fmax(phi, -a.clip), a.clip);
+        }
+        o[x] = (float)phi;
     }
 }
 
@@ -526,4 +623,60 @@ extern "C" int csu_edt(int B, int H, int W, int dtype, const void* mask, double 
     else
         launch_rows<false, true>(rgrid, W, a, st);
     return check_launch("edt");
+}
+
+// ---- signed distance maps of a label map's classes (the boundary loss's phi) --------------------------
+static const char* check_signed(int B, int C, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return "B, H and W must be >= 1";
+    if (H > SDMAX || W > SDMAX) return "H, W <= 16383";
+    if (C < 1 || C > CMAX) return "1 <= C <= 32 classes per call";
+    if ((long)B * C * 2 > 65535) return "B * C * 2 fields must be <= 65535 per call";
+    return nullptr;
+}
+
+extern "C" size_t csu_signed_distance_workspace(int B, int C, int H, int W) {
+    if (check_signed(B, C, H, W)) return 0;
+    return up256((size_t)B * C * 2 * H * W * 2);
+}
+
+extern "C" int csu_signed_distance(int B, int C, int H, int W, int class0, int dtype, const void* labels, double sy,
+                                   double sx, double clip, void* workspace, size_t ws_bytes, float* out, int out_classes,
+                                   int out_c0, void* stream) {
+    if (const char* e = check_signed(B, C, H, W)) return fail(CSU_E_ARG, std::string("signed_distance: ") + e);
+    if (!dtype_ok(dtype)) return fail(CSU_E_ARG, "signed_distance: the label map must be CSU_SURFACE_U8 or CSU_SURFACE_I64");
+    if (!(sy > 0.0) || !(sx > 0.0) || !(sy < INFINITY) || !(sx < INFINITY))
+        return fail(CSU_E_ARG, "signed_distance: spacing must be positive and finite");
+    if (!(clip < 0.0) && !(clip > 0.0 && clip < INFINITY))
+        return fail(CSU_E_ARG, "signed_distance: clip must be positive and finite, or negative for none");
+    if (out_classes < C || out_c0 < 0 || out_c0 + C > out_classes)
+        return fail(CSU_E_ARG, "signed_distance: the C classes must lie inside the out_classes planes of out");
+    if (!labels || !workspace || !out) return fail(CSU_E_ARG, "signed_distance: null labels, workspace or out");
+    if (ws_bytes < csu_signed_distance_workspace(B, C, H, W))
+        return fail(CSU_E_WORKSPACE, "signed_distance: workspace smaller than csu_signed_distance_workspace(B, C, H, W)");
+    hipStream_t st = as_stream(stream);
+    const int pairs = B * C;
+    unsigned short* g = (unsigned short*)workspace;
+    launch_columns<SITE_EQ>(dtype, pairs, C, H, W, 2, 0, class0, labels, g, st);
+    launch_columns<SITE_NE>(dtype, pairs, C, H, W, 2, 1, class0, labels, g, st);
+    SignedArgs a;
+    a.H = H; a.W = W; a.C = C; a.out_classes = out_classes; a.out_c0 = out_c0;
+    a.sy2 = (float)(sy * sy); a.sx2 = (float)(sx * sx);
+    a.s2 = sy * sy; a.step = std::min(sy, sx); a.clip = clip;
+    // columns from sx k >= clip + step on lie beyond every value the clip lets through; one more for the rounding
+    const double kcut = clip > 0.0 ? std::ceil((clip + a.step) / sx) + 1.0 : (double)W;
+    a.kmax = (int)std::min<double>(kcut, (double)W);
+    a.g = g;
+    a.out = out;
+    const size_t lds = ((size_t)((W + 7) & ~7) * 2 + (size_t)W * 2 + 15) & ~(size_t)15;
+    const dim3 grid((unsigned)H, (unsigned)pairs);
+    const bool iso = sy == sx;
+    // as launch_rows: the longest rows fill 64 KiB and __syncthreads_or keeps a few words of its own
+    if (lds + 1024 > 65536)
+        (void)hipFuncSetAttribute(iso ? (const void*)signed_row_kernel<true> : (const void*)signed_row_kernel<false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (iso)
+        signed_row_kernel<true><<<grid, NT, lds, st>>>(a);
+    else
+        signed_row_kernel<false><<<grid, NT, lds, st>>>(a);
+    return check_launch("signed_distance");
 }

@@ -11,13 +11,14 @@ from .simam import SimAM, simam
 from .unet import DoubleConv, Down, UNet, Up
 from .train import (bce_loss, dice_coefficient, evaluate_model, iou_score, make_optimizer, make_scheduler,
                     train_model, train_step)
-from .losses import (MultiClassSegLoss, SegLoss, bce_dice_loss, ce_dice_loss, ce_loss, dice_loss, multiclass_dice_loss,
-                     tversky_loss)
+from .losses import (BoundarySegLoss, MultiClassSegLoss, SegLoss, bce_dice_loss, boundary_loss, ce_dice_boundary_loss,
+                     ce_dice_loss, ce_loss, dice_loss, linear_ramp, multiclass_dice_loss, tversky_loss)
 from .optim import FusedAdam, FusedAdamW
 from .ema import WeightEMA
 from .infer import (SlidingWindowPredictor, evaluate_full_res, plan_axis, plan_tiles, reference_predict, window_1d)
 from .metrics import (SurfaceMetrics, distance_transform_edt, reference_distance_transform_edt,
                       reference_surface_metrics, surface_metrics)
+from .boundary import reference_signed_distance_map, signed_distance_map
 from .components import (PostProcess, connected_components, postprocess_labels, reference_connected_components,
                          reference_postprocess_labels)
 from .augment import SpatialAugment, reference_augment
@@ -32,4 +33,6 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "SlidingWindowPredictor", "reference_predict", "evaluate_full_res", "plan_axis", "plan_tiles", "window_1d",
            "SurfaceMetrics", "surface_metrics", "reference_surface_metrics", "distance_transform_edt",
            "reference_distance_transform_edt", "connected_components", "postprocess_labels", "PostProcess",
-           "reference_connected_components", "reference_postprocess_labels", "SpatialAugment", "reference_augment"]
+           "reference_connected_components", "reference_postprocess_labels", "SpatialAugment", "reference_augment",
+           "BoundarySegLoss", "boundary_loss", "ce_dice_boundary_loss", "linear_ramp", "signed_distance_map",
+           "reference_signed_distance_map"]

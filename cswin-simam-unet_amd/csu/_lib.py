@@ -237,6 +237,9 @@ _SIGS = {
     "csu_edt_workspace": (c_size_t, [ctypes.c_int] * 3),
     "csu_edt": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_size_t,
                                                     c_void_p, c_void_p]),
+    "csu_signed_distance_workspace": (c_size_t, [ctypes.c_int] * 4),
+    "csu_signed_distance": (ctypes.c_int, [ctypes.c_int] * 6 + [c_void_p] + [ctypes.c_double] * 3
+                            + [c_void_p, c_size_t, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p]),
     "csu_ccl_workspace": (c_size_t, [ctypes.c_int] * 3),
     "csu_ccl": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p, ctypes.c_int, c_void_p, c_size_t] + [c_void_p] * 4),
     "csu_cc_filter_workspace": (c_size_t, [ctypes.c_int] * 3),
@@ -268,6 +271,15 @@ _SIGS = {
     "csu_seg_ce_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p]
                        + [ctypes.c_long] * 3 + [ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_long, c_void_p]
                        + [c_void_p, c_void_p, c_float, c_float, ctypes.c_int, c_void_p, c_void_p]),
+    "csu_seg_bd_workspace": (c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_long]),
+    "csu_seg_bd_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p]
+                       + [ctypes.c_long] * 3 + [ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_long, c_void_p]
+                       + [c_float] * 5 + [ctypes.c_int, c_void_p, c_void_p, ctypes.c_int] + [c_void_p] * 5
+                       + [c_size_t, c_void_p]),
+    "csu_seg_bd_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p]
+                       + [ctypes.c_long] * 3 + [ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_long, c_void_p]
+                       + [c_void_p, c_void_p, c_float, c_float, ctypes.c_int, c_void_p, c_void_p, ctypes.c_int, c_void_p,
+                          c_void_p]),
     "csu_pack_nhwc_bf16": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p,
                                           c_void_p, c_void_p]),
     "csu_stripe_lepe_wgrad": (ctypes.c_int, [ctypes.POINTER(StripeArgs), ctypes.c_int, c_void_p, c_void_p, c_void_p, c_size_t,

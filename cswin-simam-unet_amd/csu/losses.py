@@ -1,5 +1,6 @@
 """Training criteria beyond nn.BCELoss: soft Dice, BCE + Dice, Tversky (binary, ``SegLoss``) and softmax
-cross-entropy + per-class Dice / Tversky on integer label maps (``MultiClassSegLoss``, at the end).
+cross-entropy + per-class Dice / Tversky on integer label maps (``MultiClassSegLoss``), and that with the boundary
+loss of signed distance maps on top (``BoundarySegLoss``, at the end).
 
 One family, ``SegLoss``:  ``bce * BCE + tversky * mean_r(1 - TI_r)`` on probabilities ``p`` and
 targets ``t`` viewed as rows (one row for the whole batch, or one per image), with
@@ -138,6 +139,8 @@ class MultiClassSegLoss:
     stats come from the fused csu_seg_ce kernels; more classes take the same formula in torch ops on
     the device.  Hashable by identity."""
 
+    _other_terms = False      # a subclass with a term of its own may have ce = tversky = 0
+
     def __init__(self, num_classes: int, ce: float = 1.0, tversky: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
                  smooth: float = 0.5, class_weight=None, ignore_index: int = -100, per_sample: bool = False,
                  include_background: bool = True):
@@ -148,7 +151,7 @@ class MultiClassSegLoss:
                 raise ValueError(f"MultiClassSegLoss: {k} must be a finite number >= 0 (got {v!r})")
         if not 0.0 < float(smooth) < float("inf"):
             raise ValueError(f"MultiClassSegLoss: smooth must be > 0 (got {smooth!r})")
-        if float(ce) == 0.0 and float(tversky) == 0.0:
+        if float(ce) == 0.0 and float(tversky) == 0.0 and not self._other_terms:
             raise ValueError("MultiClassSegLoss: ce and tversky are both zero")
         if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
             raise ValueError(f"MultiClassSegLoss: ignore_index must be an integer (got {ignore_index!r})")
@@ -227,7 +230,8 @@ class MultiClassSegLoss:
         f = torch.float64
         return torch.stack([(pm & tm).sum((1, 2)).to(f), pm.sum((1, 2)).to(f), tm.sum((1, 2)).to(f)])
 
-    def _run(self, logits, target, with_stats):
+    def _label_map(self, logits, target):
+        """The target as a (B, *spatial) label map, after the shape and dtype checks."""
         K = self.num_classes
         if logits.dim() < 3 or logits.shape[1] != K:
             raise ValueError(f"MultiClassSegLoss: logits (B, {K}, H, W) (got {tuple(logits.shape)})")
@@ -236,6 +240,11 @@ class MultiClassSegLoss:
         if target.dtype not in (torch.int64, torch.uint8) or \
                 tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
             raise ValueError("MultiClassSegLoss: an int64 or uint8 label map (B, H, W) or (B, 1, H, W) of the logits' size")
+        return target
+
+    def _run(self, logits, target, with_stats):
+        K = self.num_classes
+        target = self._label_map(logits, target)
         with torch.autocast(logits.device.type, enabled=False):
             if logits.is_cuda and K <= 32:
                 from . import ops
@@ -275,3 +284,165 @@ def multiclass_dice_loss(num_classes: int, smooth: float = 1e-6, ignore_index: i
     """Mean over classes of the soft Dice loss 1 - (2 sum p_c [t = c] + smooth) / (sum p_c + sum [t = c] + smooth)."""
     return MultiClassSegLoss(num_classes, ce=0.0, tversky=1.0, alpha=0.5, beta=0.5, smooth=smooth / 2,
                              ignore_index=ignore_index, per_sample=per_sample, include_background=include_background)
+
+
+class BoundarySegLoss(MultiClassSegLoss):
+    """``MultiClassSegLoss`` plus the boundary loss of Kervadec et al. ("Boundary loss for highly unbalanced
+    segmentation", 2019), the term that moves HD95 where CE + Dice move the overlap:
+
+        n  = sum_c T_c                                      (live pixels whose label is a class, whole batch),
+        BD = (1 / (n |Cb|)) sum over live pixels, c in Cb of softmax(z)_c phi_c      (0 when n = 0),
+        loss = ce * CE + tversky * mean_r mean_{c in C} (1 - TI_rc) + boundary_weight * BD,
+
+    phi_c = the signed distance of the pixel to the border of class c in the target, negative inside the
+    class (``csu.boundary.signed_distance_map``: ``spacing`` and ``clip`` go there); Cb = classes 1 .. K-1, or
+    all with ``boundary_background``.  ``ce = tversky = 0`` is legal here (the boundary term alone).
+
+    ``criterion(logits, target, dist=None)`` and ``criterion.loss_stats(logits, target, dist=None)``: without
+    ``dist`` (fp32 (B, K, H, W) maps made beforehand) the maps are made from ``target`` in the same call, on
+    its device -- on the GPU by csu_signed_distance with no host synchronisation, so labels that were
+    augmented on the device this step are fine and the whole call can be captured in a graph.  On the GPU
+    with K <= 32 the loss and its gradient come from the fused csu_seg_bd kernels; CPU tensors and more
+    classes take the same formula in torch ops.
+
+    The weight lives in a one-element device tensor the kernels read: ``set_boundary_weight(w)`` fills it in
+    place, so a captured graph follows a schedule without a re-capture; ``boundary_weight`` is the host
+    copy.  ``schedule``: a callable epoch -> weight (``linear_ramp`` is the authors' rebalancing), applied by
+    ``on_epoch(epoch)``, which csu.train.train_model calls at the start of every epoch.  ``last_terms``: the
+    (2,) device tensor (loss without the boundary term, BD) of the last call."""
+
+    _other_terms = True
+
+    def __init__(self, num_classes: int, ce: float = 1.0, tversky: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
+                 smooth: float = 0.5, class_weight=None, ignore_index: int = -100, per_sample: bool = False,
+                 include_background: bool = True, boundary: float = 1.0, boundary_background: bool = False,
+                 spacing=(1.0, 1.0), clip=None, schedule=None):
+        super().__init__(num_classes, ce, tversky, alpha, beta, smooth, class_weight, ignore_index, per_sample,
+                         include_background)
+        if not float(boundary) >= 0.0 or float(boundary) == float("inf"):
+            raise ValueError(f"BoundarySegLoss: boundary must be a finite number >= 0 (got {boundary!r})")
+        try:
+            sy, sx = (float(v) for v in spacing)
+        except (TypeError, ValueError):
+            raise ValueError(f"BoundarySegLoss: spacing = (sy, sx) (got {spacing!r})") from None
+        if not (0.0 < sy < float("inf") and 0.0 < sx < float("inf")):
+            raise ValueError(f"BoundarySegLoss: spacing must be positive and finite (got {spacing!r})")
+        if clip is not None and not 0.0 < float(clip) < float("inf"):
+            raise ValueError(f"BoundarySegLoss: clip must be positive and finite, or None (got {clip!r})")
+        if schedule is not None and not callable(schedule):
+            raise ValueError("BoundarySegLoss: schedule is a callable epoch -> weight, or None")
+        self.boundary_background, self.spacing = bool(boundary_background), (sy, sx)
+        self.clip, self.schedule = None if clip is None else float(clip), schedule
+        self._w, self._wbd = float(boundary), {}
+        self.last_terms = None
+
+    def __repr__(self):
+        return (f"BoundarySegLoss({super().__repr__()[len('MultiClassSegLoss('):-1]}, boundary={self._w}, "
+                f"boundary_background={self.boundary_background}, spacing={self.spacing}, clip={self.clip}, "
+                f"schedule={self.schedule!r})")
+
+    @property
+    def boundary_weight(self) -> float:
+        """The current weight of the boundary term (the host copy of the device scalar)."""
+        return self._w
+
+    def set_boundary_weight(self, w: float) -> None:
+        """Set the weight; every device's scalar is filled in place (no re-capture, no synchronisation)."""
+        if not float(w) >= 0.0 or float(w) == float("inf"):
+            raise ValueError(f"BoundarySegLoss: the boundary weight must be a finite number >= 0 (got {w!r})")
+        self._w = float(w)
+        for t in self._wbd.values():
+            t.fill_(self._w)
+
+    def on_epoch(self, epoch: int) -> None:
+        """Apply the schedule, if there is one, for the epoch that starts (0-based)."""
+        if self.schedule is not None:
+            self.set_boundary_weight(self.schedule(int(epoch)))
+
+    def _scalar(self, device):
+        t = self._wbd.get(device)
+        if t is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("BoundarySegLoss: call the criterion once on this device before capturing it in a "
+                                   "graph (the weight's device scalar is made at the first call)")
+            t = self._wbd[device] = torch.full((1,), self._w, dtype=torch.float32, device=device)
+        return t
+
+    def _boundary_torch(self, z, t, phi):
+        """BD in torch ops, in z's floating dtype: z, phi (B, K, *), t (B, *) int64."""
+        K = z.shape[1]
+        live = t != self.ignore_index
+        n = (live & (t >= 0) & (t < K)).sum().to(z.dtype)
+        first = 0 if self.boundary_background else 1
+        p = torch.softmax(z, 1) * live.unsqueeze(1).to(z.dtype)
+        s = (p[:, first:] * phi[:, first:].to(z.dtype)).sum()
+        den = n * (K - first)
+        return torch.where(n > 0, s / torch.where(n > 0, den, torch.ones_like(den)), s * 0.0)
+
+    def _run(self, logits, target, with_stats, dist=None):
+        K = self.num_classes
+        target = self._label_map(logits, target)
+        with torch.autocast(logits.device.type, enabled=False):
+            if dist is None:
+                from .boundary import signed_distance_map
+                if target.dim() != 3:
+                    raise ValueError("BoundarySegLoss: distance maps are made of (B, H, W) label maps; pass dist= otherwise")
+                dist = signed_distance_map(target, K, self.spacing, self.clip)
+            elif not isinstance(dist, torch.Tensor) or not dist.is_floating_point() or dist.shape != logits.shape \
+                    or dist.device != logits.device:
+                raise ValueError("BoundarySegLoss: dist is a floating-point tensor of the logits' shape on their device")
+            dist = dist.detach().float()
+            w = self._scalar(logits.device)
+            if logits.is_cuda and K <= 32:
+                from . import ops
+                z = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
+                rows = logits.shape[0] if self.per_sample else 1
+                res = ops.seg_bd(z, target, dist, w, self.params, self._weight(logits.device), self.ignore_index, rows,
+                                 self.include_background, self.boundary_background, with_stats)
+                self.last_terms = res[1]
+                return (res[0], res[2]) if with_stats else res[0]
+            z, t = logits.float(), target.long()
+            base, bd = self._torch(z, t), self._boundary_torch(z, t, dist)
+            self.last_terms = torch.stack([base.detach(), bd.detach()])
+            loss = base + w[0] * bd
+            if not with_stats:
+                return loss
+            return loss, self.hard_stats(z.detach(), t)
+
+    def __call__(self, logits: torch.Tensor, target: torch.Tensor, dist: torch.Tensor = None) -> torch.Tensor:
+        return self._run(logits, target, False, dist)
+
+    def loss_stats(self, logits: torch.Tensor, target: torch.Tensor, dist: torch.Tensor = None):
+        """The loss and the hard per-class sums (3, K) fp64 of the same pass."""
+        return self._run(logits, target, True, dist)
+
+
+def linear_ramp(start: float = 0.01, step: float = 0.01, stop: float = 1.0):
+    """The boundary weight of epoch e (0-based): start + step * e, at most ``stop`` -- Kervadec's rebalancing,
+    which lets the region terms shape the prediction first.  For ``BoundarySegLoss(schedule=...)``."""
+    start, step, stop = float(start), float(step), float(stop)
+    if not (0.0 <= start <= stop < float("inf")) or not 0.0 <= step < float("inf"):
+        raise ValueError("linear_ramp: 0 <= start <= stop and step >= 0, all finite")
+
+    def weight(epoch: int) -> float:
+        return min(stop, start + step * int(epoch))
+
+    return weight
+
+
+def boundary_loss(num_classes: int, ignore_index: int = -100, boundary_background: bool = False, spacing=(1.0, 1.0),
+                  clip=None, schedule=None) -> BoundarySegLoss:
+    """The boundary term alone (weight 1), with the per-class metrics of MultiClassSegLoss."""
+    return BoundarySegLoss(num_classes, ce=0.0, tversky=0.0, ignore_index=ignore_index, boundary=1.0,
+                           boundary_background=boundary_background, spacing=spacing, clip=clip, schedule=schedule)
+
+
+def ce_dice_boundary_loss(num_classes: int, ce: float = 1.0, dice: float = 1.0, boundary: float = 1.0, smooth: float = 1.0,
+                          class_weight=None, ignore_index: int = -100, per_sample: bool = False,
+                          include_background: bool = True, boundary_background: bool = False, spacing=(1.0, 1.0),
+                          clip=None, schedule=None) -> BoundarySegLoss:
+    """ce * CE + dice * mean over classes of (1 - Dice_c) + boundary * BD; smooth is Dice's, as in ce_dice_loss."""
+    return BoundarySegLoss(num_classes, ce=ce, tversky=dice, alpha=0.5, beta=0.5, smooth=smooth / 2,
+                           class_weight=class_weight, ignore_index=ignore_index, per_sample=per_sample,
+                           include_background=include_background, boundary=boundary,
+                           boundary_background=boundary_background, spacing=spacing, clip=clip, schedule=schedule)

@@ -1565,6 +1565,131 @@ def seg_ce(logits: torch.Tensor, target: torch.Tensor, params, class_weight: Opt
                           bool(with_stats))
 
 
+class _SegBDFn(torch.autograd.Function):
+    """_SegCEFn's loss plus the boundary term w_bd[0] * BD, BD = the mean over the live pixels and the classes
+    of Cb (1 .. K-1, or all with bd_background) of softmax(z)_c * phi_c (csu_seg_bd_fwd / csu_seg_bd_bwd: the
+    same kernels with one more partial sum and phi read per class plane).  phi: fp32 (B, K, *spatial) signed
+    distance maps, not differentiated; w_bd: a one-element fp32 device tensor the kernels read, so its value
+    may change between replays of a captured graph.  Also returns terms = (loss without the boundary term,
+    BD) as a non-differentiable fp32 (2,) tensor."""
+
+    @staticmethod
+    def forward(ctx, z, t, phi, w_bd, params, cw, ignore_index: int, rows: int, include_background: bool,
+                bd_background: bool, with_stats: bool = False):
+        B, K = z.shape[0], z.shape[1]
+        z, sb, sk, sp, HW, pad_ok = _seg_ce_layout(z)
+        t = t.contiguous()
+        phi = phi.contiguous()
+        w_ce, w_tv, alpha, beta, smooth = (float(v) for v in params)
+        dev = z.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(2, dtype=torch.float32, device=dev)
+        stats = torch.empty(3, K, dtype=torch.float64, device=dev) if with_stats else None
+        coef = torch.empty(2 * rows * K + 2, dtype=torch.float32, device=dev)
+        nws = lib().csu_seg_bd_workspace(B, K, HW)
+        ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        lab = 1 if t.dtype == torch.int64 else 0
+        geom = (B, K, HW, rows, dtype_code(z), sb, sk, sp, int(pad_ok), lab, int(ignore_index), int(include_background),
+                int(bd_background))
+        nbytes = B * K * HW * (z.element_size() + 4) + B * HW * t.element_size()
+        _launch("seg_bd", lambda: lib().csu_seg_bd_fwd(B, K, HW, rows, geom[4], ptr(z), sb, sk, sp, geom[8], lab, ptr(t),
+                                                       geom[10], ptr(cw), w_ce, w_tv, alpha, beta, smooth, geom[11],
+                                                       ptr(phi), ptr(w_bd), geom[12], ptr(loss), ptr(terms), ptr(stats),
+                                                       ptr(coef), ptr(ws), nws, stream_ptr(dev)),
+                (14 * K + 30) * B * HW, nbytes, prec="f32")
+        ctx.save_for_backward(z, t, phi, w_bd, coef, cw)
+        ctx.seg = (geom, w_ce, w_tv, nbytes)
+        if with_stats:
+            ctx.mark_non_differentiable(terms, stats)
+            return loss, terms, stats
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        z, t, phi, w_bd, coef, cw = ctx.saved_tensors
+        (B, K, HW, rows, dt, sb, sk, sp, pad_ok, lab, ignore, bg, bdbg), w_ce, w_tv, nbytes = ctx.seg
+        g = g.float().contiguous()
+        es = z.element_size()      # dz: the logits' strides and offset within 16 B, as _SegCEFn.backward
+        off = (z.data_ptr() % 16) // es
+        need = (B - 1) * sb + (HW - 1) * sp + max((K - 1) * sk + 1, _seg_ce_bucket(K) if pad_ok else 0)
+        dz = torch.empty(off + need, dtype=z.dtype, device=z.device).as_strided(z.shape, z.stride(), off)
+        _launch("seg_bd_bwd", lambda: lib().csu_seg_bd_bwd(B, K, HW, rows, dt, ptr(z), sb, sk, sp, pad_ok, lab, ptr(t), ignore,
+                                                           ptr(cw), ptr(g), ptr(coef), w_ce, w_tv, bg, ptr(phi), ptr(w_bd),
+                                                           bdbg, ptr(dz), stream_ptr(z.device)),
+                (18 * K + 20) * B * HW, nbytes + B * K * HW * es, prec="f32")
+        return (dz,) + (None,) * 10
+
+
+def seg_bd(logits: torch.Tensor, target: torch.Tensor, phi: torch.Tensor, w_bd: torch.Tensor, params,
+           class_weight: Optional[torch.Tensor] = None, ignore_index: int = -100, rows: int = 1,
+           include_background: bool = True, bd_background: bool = False, with_stats: bool = False):
+    """seg_ce's loss plus w_bd[0] times the boundary term of fp32 signed distance maps phi (B, K, *spatial) (see
+    _SegBDFn; signed_distance makes the maps).  w_bd: a one-element fp32 device tensor; params = (w_ce,
+    w_tversky, alpha, beta, smooth), where both weights may be zero.  Returns (loss, terms) or, with_stats,
+    (loss, terms, fp64 (3, K) hard sums); terms = (loss without the boundary term, BD)."""
+    require_device(logits, target, phi, w_bd, class_weight)
+    if logits.dim() < 2 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("seg_bd: fp32 or bf16 logits (B, K, *spatial)")
+    B, K = logits.shape[0], logits.shape[1]
+    if not 2 <= K <= SEG_CE_MAX_CLASSES:
+        raise ValueError(f"seg_bd: 2 <= K <= {SEG_CE_MAX_CLASSES} classes (got {K})")
+    if target.dtype not in (torch.int64, torch.uint8) or tuple(target.shape) != (B,) + tuple(logits.shape[2:]):
+        raise ValueError("seg_bd: int64 or uint8 target of the logits' shape without the class dim")
+    if logits.numel() < 1:
+        raise ValueError("seg_bd: empty logits")
+    if phi.dtype != torch.float32 or phi.shape != logits.shape:
+        raise ValueError("seg_bd: phi is an fp32 tensor of the logits' shape")
+    if w_bd.dtype != torch.float32 or w_bd.numel() != 1:
+        raise ValueError("seg_bd: w_bd is a one-element fp32 tensor")
+    rows = int(rows)
+    if rows not in (1, B):
+        raise ValueError("seg_bd: rows must be 1 or the batch size")
+    if len(params) != 5:
+        raise ValueError("seg_bd: params = (w_ce, w_tversky, alpha, beta, smooth)")
+    if class_weight is not None:
+        if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (K,):
+            raise ValueError("seg_bd: class_weight is an fp32 (K,) tensor")
+        class_weight = class_weight.contiguous()
+    return _SegBDFn.apply(logits, target, phi.detach(), w_bd.detach(), tuple(params), class_weight, int(ignore_index), rows,
+                          bool(include_background), bool(bd_background), bool(with_stats))
+
+
+SIGNED_DISTANCE_MAX_DIM = 16383
+
+
+def signed_distance(labels: torch.Tensor, class0: int, classes: int, out: torch.Tensor, out_c0: int = 0,
+                    spacing: Sequence[float] = (1.0, 1.0), clip: Optional[float] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """csu_signed_distance: the signed distance maps of label values class0 .. class0 + classes - 1 of a
+    contiguous uint8 / int64 device label map (B, H, W), written into planes out_c0 .. of the fp32
+    (B, C_out, H, W) tensor ``out`` (csrc/surface.hip; csu.boundary.signed_distance_map is the public form and
+    states the definition).  workspace: a uint8 buffer of at least csu_signed_distance_workspace bytes to
+    reuse, or None.  Returns the workspace it used."""
+    require_device(labels, out)
+    if labels.dim() != 3 or labels.dtype not in (torch.uint8, torch.int64) or not labels.is_contiguous():
+        raise ValueError("signed_distance: a contiguous uint8 or int64 label map (B, H, W)")
+    B, H, W = labels.shape
+    if out.dtype != torch.float32 or out.dim() != 4 or not out.is_contiguous() or \
+            (out.shape[0], out.shape[2], out.shape[3]) != (B, H, W):
+        raise ValueError("signed_distance: out is a contiguous fp32 (B, C_out, H, W) tensor of the label map's size")
+    if H > SIGNED_DISTANCE_MAX_DIM or W > SIGNED_DISTANCE_MAX_DIM:
+        raise ValueError(f"signed_distance: H, W <= {SIGNED_DISTANCE_MAX_DIM} (got {H} x {W})")
+    sy, sx = (float(v) for v in spacing)
+    cl = -1.0 if clip is None else float(clip)
+    C = int(classes)
+    need = lib().csu_signed_distance_workspace(B, C, H, W)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=labels.device)
+    ws = workspace
+    _launch("signed_distance",
+            lambda: lib().csu_signed_distance(B, C, H, W, int(class0), 0 if labels.dtype == torch.uint8 else 1, ptr(labels),
+                                              sy, sx, cl, ptr(ws), ws.numel(), ptr(out), out.shape[1], int(out_c0),
+                                              stream_ptr(labels.device)),
+            0, B * C * H * W * (2 * labels.element_size() + 16), prec="f32")
+    return ws
+
+
 def augment_batch(images: torch.Tensor, masks: torch.Tensor, params) -> Tuple[torch.Tensor, torch.Tensor]:
     """csu_augment_batch: uint8 (B, S, S, 3) images / (B, S, S) masks on the device, params per image
     (hflip, vflip, clockwise quarter turns, top, left, crop_h, crop_w) -> fp32 (B, 3, S, S) and

@@ -422,7 +422,11 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     ``ema.applied()`` through the same evaluate_model (and the same cached eval graph), which adds
     ``ema_test_loss``, ``ema_test_dice`` and ``ema_test_iou`` (multi-class: also ``ema_test_class_dice`` and
     ``ema_test_class_iou``); the scheduler keeps stepping on the raw ``test_loss``, and checkpoints
-    carry the EMA.  Without an EMA the history has exactly the keys above."""
+    carry the EMA.  Without an EMA the history has exactly the keys above.
+    Schedules: a criterion with an ``on_epoch(epoch)`` method (csu.losses.BoundarySegLoss) gets that call at the
+    start of every epoch, before the first step; one with a ``boundary_weight`` adds the history key
+    ``boundary_weight``, the weight each epoch trained with.  The weight is a device scalar the captured step
+    reads, so the change needs no re-capture."""
     history = {"train_loss": [], "train_dice": [], "train_iou": [], "test_loss": [], "test_dice": [], "test_iou": [],
                "learning_rates": []}
     clips = _clips(optimizer)
@@ -434,6 +438,8 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
         optimizer.ema = ema      # an EMA passed here alone: the optimizer (FusedAdamW) or train_step updates it
     if ema is not None:
         history["ema_test_loss"], history["ema_test_dice"], history["ema_test_iou"] = [], [], []
+    if hasattr(criterion, "boundary_weight"):
+        history["boundary_weight"] = []
     rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
     start = 0
     if resume_from is not None:
@@ -452,6 +458,10 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     if cache is not None:
         _drop_stale_train_graphs(cache, optimizer, reducer)
     for epoch in range(start, num_epochs):
+        if hasattr(criterion, "on_epoch"):      # a weight schedule; a captured step reads the weight from the device
+            criterion.on_epoch(epoch)
+        if hasattr(criterion, "boundary_weight"):
+            history["boundary_weight"].append(criterion.boundary_weight)
         model.train()
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):

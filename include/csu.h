@@ -879,6 +879,37 @@ int csu_seg_ce_bwd(int B, int K, long HW, int rows, int dtype, const void* z, lo
                    const float* coef, float w_ce, float w_tversky, int include_background, void* dz, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The same loss with a boundary term (Kervadec et al. 2019, "Boundary loss for highly unbalanced
+ * segmentation"; csrc/seg_ce.hip, the kernels above with one compile-time flag set); the reference has
+ * no counterpart.  Every argument of csu_seg_ce_* keeps its meaning; added:
+ *   phi:  dense fp32 (B, K, HW), phi[b, c, pix] = the signed distance of the pixel to the border of class c
+ *         in the label map (csu_signed_distance: negative inside the class); read as data, must be finite.
+ *   w_bd: one float on the device, read by the kernels, so a schedule can change the weight between
+ *         replays of a captured graph.  It is not checked.
+ *   bd_background: 0 = the classes 1 .. K-1 carry the term, 1 = all K classes; that set is Cb.
+ *   n  = sum_c T_c                                     (the live pixels whose label is a class, whole batch)
+ *   BD = (1 / (n |Cb|)) sum over live pixels, c in Cb of p_c phi_c               (0 when n = 0)
+ *   loss[0] = [w_ce CE + w_tversky ...] + w_bd[0] BD;  terms[0] = the bracket, terms[1] = BD
+ *   dz_k   += dloss[0] w_bd[0] / (n |Cb|) p_k (f_k - sum_c f_c p_c),   f_c = phi_c for c in Cb, else 0
+ * fwd keeps one more partial sum per (image, chunk) item, in the same fixed order, divides in fp64 and
+ * leaves 1 / (n |Cb|) behind 1 / sum w in coef (2 rows K + 2 floats).  Workspace csu_seg_bd_workspace(B, K,
+ * HW) bytes = (3 + 5 K) floats per item (0: bad arguments).  w_ce = w_tversky = 0 is legal here.
+ * Ignored pixels contribute nothing and get a zero gradient; deterministic, no atomics.  With w_bd[0] = 0
+ * the loss and dz equal those of csu_seg_ce_* on the same inputs.
+ * CSU_E_ARG: as csu_seg_ce_* (but for the two zero weights), a null phi, w_bd or terms.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_seg_bd_workspace(int B, int K, long HW);
+int csu_seg_bd_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix, int pad_ok,
+                   int label_dtype, const void* t, long ignore_index, const float* class_weight, float w_ce,
+                   float w_tversky, float alpha, float beta, float smooth, int include_background, const float* phi,
+                   const float* w_bd, int bd_background, float* loss, float* terms, double* stats, float* coef,
+                   void* workspace, size_t ws_bytes, void* stream);
+int csu_seg_bd_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix, int pad_ok,
+                   int label_dtype, const void* t, long ignore_index, const float* class_weight, const float* dloss,
+                   const float* coef, float w_ce, float w_tversky, int include_background, const float* phi,
+                   const float* w_bd, int bd_background, void* dz, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mask-aligned batch augmentation (AugmentationTransform cswin:20-87 + the dataset's /255 and
  * HWC -> CHW, cswin:166-173), square S x S images: img uint8 (B, S, S, 3), mask uint8 (B, S, S),
  * params int32 (B, 7) on the device = {hflip, vflip, clockwise quarter turns 0..3, crop top,
@@ -1042,6 +1073,33 @@ int csu_surface_metrics(int B, int C, int H, int W, int mode, int class0, int pr
 size_t csu_edt_workspace(int B, int H, int W);
 int csu_edt(int B, int H, int W, int dtype, const void* mask, double sy, double sx, void* workspace, size_t ws_bytes,
             float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Signed distance maps of a label map's classes (csrc/surface.hip): phi of the boundary loss
+ * (csu_seg_bd_*), Kervadec's one_hot2dist; the reference has no counterpart.
+ *   labels: (B, H, W), contiguous, CSU_SURFACE_U8 or CSU_SURFACE_I64, read in place.  For image b and class c
+ *   (label value class0 + c) M is the set of pixels that hold the value.  A pixel with any other value, an
+ *   ignore_index included, is outside every class.  Beyond the image there is nothing: the image edge is
+ *   no border (unlike the surface metrics above).  With S = diag(sy, sx):
+ *      M empty or the whole image:  phi = 0 everywhere;
+ *      x not in M:  phi(x) =   min over y in M     of |S (x - y)|;
+ *      x in M:      phi(x) = -(min over y not in M of |S (x - y)| - min(sy, sx)),  0 on the inner border;
+ *   with unit spacing edt(neg) neg - (edt(pos) - 1) pos.  clip > 0: phi is clamped to [-clip, clip] (and the row
+ *   search stops at that radius); clip < 0: none.
+ *   out fp32 (B, out_classes, H, W), class c written at plane out_c0 + c.
+ * The column pass of the transform above runs twice per (image, class), with the pixels on and off the
+ * class as sites, into two uint16 fields; one row pass stages the row of both in LDS and searches, for
+ * every pixel, the field of the other side.  sy == sx: int32 index distances (exact); otherwise fp32.  No
+ * atomics, no synchronisation, capturable; results are bitwise repeatable and do not depend on B, C or
+ * the chunking.  Workspace csu_signed_distance_workspace(B, C, H, W) = 4 B C H W bytes rounded up to 256.
+ * CSU_E_ARG: a size < 1, H or W > 16383 (the rows of two fields fill 64 KiB of LDS), C > 32, B C 2 > 65535,
+ *      an unknown dtype, a spacing that is not positive and finite, clip 0 / inf / NaN, classes outside the
+ *      out planes, a null pointer.  CSU_E_WORKSPACE: workspace too small.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_signed_distance_workspace(int B, int C, int H, int W);
+int csu_signed_distance(int B, int C, int H, int W, int class0, int dtype, const void* labels, double sy, double sx,
+                        double clip, void* workspace, size_t ws_bytes, float* out, int out_classes, int out_c0,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Connected-component labelling and the component rules of segmentation post-processing
