@@ -2333,7 +2333,7 @@ def mlp_residual(res, x, fc1: torch.nn.Linear, fc2: torch.nn.Linear, drop: Optio
     output is computed in the same launch and attached to the output for layer_norm_fork."""
     C = x.shape[-1]
     ln = _usable_ln_next(ln_next, C, FUSE_NEXT_LN)
-    y = mlp_fp8(res, x, fc1, fc2, drop, ln=None if FP8_QKV else ln)   # FP8_QKV: norm1 is the e4m3 LN
+    y = mlp_fp8(res, x, fc1, fc2, drop, ln=ln)
     if y is not None:
         return y
     args = (res, x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, _weight_bf16(fc1.weight), _weight_bf16(fc2.weight), drop)
@@ -2711,13 +2711,6 @@ class Fp8Weights:
             return None
         return e[1:]
 
-    def lookup(self, w):
-        """(e4m3 bytes, row scales) of a quantised weight, or None."""
-        i = self.index.get(w.data_ptr())
-        if i is None or self.params[i].shape != w.shape:
-            return None
-        return self.q[i], self.scales[i]
-
     def valid_for(self, params) -> bool:
         params = list(params)
         return len(params) == len(self.params) and all(a is b and a.data_ptr() == q
@@ -2795,95 +2788,6 @@ def set_cast_cache(cache: Optional[CastCache], fp8: Optional[Fp8Weights] = None)
     global _ACTIVE_CACHE, _ACTIVE_FP8
     _ACTIVE_CACHE = cache
     _ACTIVE_FP8 = fp8
-
-
-def fp8_gemm(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Tensor,
-             bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """bf16 (M, N) = (aq * sa[:, None]) @ (wq * sw[:, None])^T + bias on e4m3 MFMA (csu_fp8_gemm):
-    aq (M, K) / wq (N, K) uint8 e4m3fn bytes, sa / sw fp32 row scales."""
-    require_device(aq, wq)
-    M, K = aq.shape
-    N = wq.shape[0]
-    if wq.shape[1] != K or sa.numel() != M or sw.numel() != N or aq.dtype != torch.uint8 or wq.dtype != torch.uint8:
-        raise ValueError("fp8_gemm: shape / dtype mismatch")
-    aq, wq, sa, sw = aq.contiguous(), wq.contiguous(), sa.float().contiguous(), sw.float().contiguous()
-    b = _f32(bias)
-    out = torch.empty(M, N, dtype=torch.bfloat16, device=aq.device)
-    _launch("fp8_gemm", lambda: lib().csu_fp8_gemm(M, N, K, ptr(aq), ptr(sa), ptr(wq), ptr(sw), ptr(b), ptr(out),
-                                                   stream_ptr(aq.device)),
-            2 * M * N * K, M * K + N * K + M * N * 2 + (M + N) * 4, prec="fp8")
-    return out
-
-
-def dequant_e4m3_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
-    """bf16 q * scale[:, None] of e4m3fn bytes (exact: power-of-two scales)."""
-    require_device(q)
-    rows, cols = q.shape
-    out = torch.empty(rows, cols, dtype=torch.bfloat16, device=q.device)
-    _launch("dequant_e4m3", lambda: lib().csu_dequant_e4m3_rows(rows, cols, ptr(q), ptr(scale), ptr(out),
-                                                                stream_ptr(q.device)),
-            0, rows * cols * 3 + rows * 4, prec="fp8")
-    return out
-
-
-def layer_norm_fp8(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5, dq: bool = False):
-    """(e4m3 bytes, row scales, mean, rstd[, bf16 dequantised copy]) of LN(x) (csu_layernorm_fwd_fp8_dq),
-    no autograd."""
-    require_device(x, weight, bias)
-    x = x.contiguous()
-    C = x.shape[-1]
-    rows = x.numel() // C
-    w = _f32(weight)
-    b = _f32(bias)
-    q = torch.empty(rows, C, dtype=torch.uint8, device=x.device)
-    s = torch.empty(rows, dtype=torch.float32, device=x.device)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    ydq = torch.empty(rows, C, dtype=torch.bfloat16, device=x.device) if dq else None
-    _launch("layernorm_fwd_fp8", lambda: lib().csu_layernorm_fwd_fp8_dq(rows, C, float(eps), dtype_code(x), ptr(x),
-                                                                        ptr(w), ptr(b), ptr(q), ptr(s), ptr(ydq),
-                                                                        ptr(mean), ptr(rstd), stream_ptr(x.device)),
-            10 * rows * C, rows * C * (esize(x) + 1 + (2 if dq else 0)) + rows * 12, prec=prec_of(x))
-    return (q, s, mean, rstd, ydq) if dq else (q, s, mean, rstd)
-
-
-class _LnLinearFp8Fn(torch.autograd.Function):
-    """Residual junction + LayerNorm + Linear with e4m3 operands (BASELINE config 5, "fp8 MFMA
-    weights"): x -> (x, LN(x) W^T + b) for CSWinBlock's norm1 -> qkv (cswin:357 -> cswin:337).
-    The LayerNorm writes its output as e4m3 with one power-of-two scale per token
-    (csu_layernorm_fwd_fp8: the kernel holds the whole token row, so the amax costs nothing) and
-    csu_fp8_gemm multiplies it with the e4m3 weight rows on v_mfma_scale_f32_32x32x64_f8f6f4.
-    Backward (straight-through for both quantisations): dh = dY W_q (bf16 GEMM on the dequantised
-    e4m3 weights, the cast cache's transpose), dW / db from dY and the dequantised e4m3 activation
-    the forward multiplied, and the norm1 backward fused with the residual gradient as in
-    _LayerNormForkFn."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, weight, bias, eps: float, wq, ws, wt):
-        x = x.contiguous()
-        C = x.shape[-1]
-        hq, hs, mean, rstd, hdq = layer_norm_fp8(x, gamma, beta, eps, dq=True)
-        y = fp8_gemm(hq, hs, wq, ws, bias).view(*x.shape[:-1], wq.shape[0])
-        ctx.save_for_backward(x, _f32(gamma), mean, rstd, hdq, wt)
-        ctx.params = (gamma, beta)
-        ctx.pdtypes = (gamma.dtype, beta.dtype)
-        ctx.lin = (weight, bias)
-        ctx.lmeta = (weight.dtype, None if bias is None else bias.dtype, C)
-        _note_use(ctx, gamma, beta, weight, bias)
-        return x.view_as(x), y
-
-    @staticmethod
-    def backward(ctx, dres, dy):
-        x, g, mean, rstd, h, wt = ctx.saved_tensors     # h: the dequantised e4m3 LN output (bf16, exact)
-        wdt, bdt, C = ctx.lmeta
-        dh = dw = db = None
-        if dy is not None:
-            N = dy.shape[-1]
-            dy2 = _bf16_of(dy).reshape(-1, N).contiguous()
-            dh = gemm(dy2, wt, False, torch.bfloat16).view(x.shape)
-            dw, db = _linear_param_grads(ctx.needs_input_grad[3:5], dy2, h, wdt, bdt, ctx.lin)
-        dx, dg, dbeta = _ln_fork_backward(ctx, x, g, mean, rstd, dres, dh)
-        return dx, dg, dbeta, dw, db, None, None, None, None
 
 
 class _LnLinearWsFn(torch.autograd.Function):
@@ -3050,29 +2954,12 @@ def ln_mlp_residual(x: torch.Tensor, ln: torch.nn.LayerNorm, fc1: torch.nn.Linea
                            _weight_bf16(fc1.weight), _weight_bf16(fc2.weight), pre, lnn)
 
 
-# qkv in the fp8 weight format.  False: the bf16 weight-streaming GEMM on the EXACT dequantised e4m3
-# weight (the cast cache's shadow), norm1 in bf16 (fused into the previous block's Mlp epilogue where
-# it can be); True: e4m3 norm1 output x e4m3 weight on the fp8 MFMA (_LnLinearFp8Fn).  Measured at
-# 1024x1024 B4: fp8 qkv 422 us/step + its e4m3 LayerNorms 303 against ~320 (gemm_ws) + a share of 138
-# for bf16 (profiles/r07zd_*): the fp8 qkv made the fp8 format slower than bf16 (340.1 vs 345.8 img/s).
-FP8_QKV = os.environ.get("CSU_FP8_QKV", "0") != "0"
-
-
-def ln_linear_fp8(x: torch.Tensor, ln: torch.nn.LayerNorm, lin: torch.nn.Linear):
-    """(x, lin(ln(x))) through _LnLinearFp8Fn when the fp8 weight format holds lin's weight (bf16
-    autocast forward of a model in set_weight_format('fp8_e4m3')) and FP8_QKV, else None."""
-    if _ACTIVE_FP8 is None or not x.is_cuda or not FP8_QKV:
-        return None
-    got = _ACTIVE_FP8.lookup(lin.weight)
-    N, K = lin.weight.shape
-    if got is None or N % 64 or K % 64 or K > 512:
-        return None
-    wc = _cached(lin.weight, torch.bfloat16)
-    if wc is None:
-        return None
-    wt = _weight_t(lin.weight, wc)      # (K, N) bf16 of the dequantised e4m3 weight: the dX GEMM's operand
-    with torch.autocast("cuda", enabled=False):
-        return _LnLinearFp8Fn.apply(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, got[0], got[1], wt)
+# qkv in the fp8 weight format is the bf16 weight-streaming GEMM on the EXACT dequantised e4m3 weight
+# (the cast cache's shadow), norm1 in bf16 (fused into the previous block's Mlp epilogue where it can
+# be).  The e4m3 norm1 output x e4m3 weight on the fp8 MFMA made the fp8 format slower than bf16 (340.1 vs
+# 345.8 img/s at 1024x1024 B4, profiles/r07zd_*) and is retired.  A plain constant, no longer
+# a switch: bench.py's dtype label still reads it.
+FP8_QKV = False
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,

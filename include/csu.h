@@ -447,24 +447,6 @@ typedef struct {
 } csu_fp8_shadow_item;
 int csu_quant_e4m3_shadow_batch(const csu_fp8_shadow_item* items, int count, long total_blocks, void* stream);
 
-/* fp8-e4m3 token GEMM (BASELINE config 5 "fp8 MFMA weights"; replaces CSWinBlock.qkv, cswin:337,
- * on the norm1 output, cswin:357):  out[m][n] = bf16(sa[m] sw[n] sum_k aq[m][k] wq[n][k] + bias[n]),
- * aq (M x K) / wq (N x K) OCP e4m3fn bytes, sa / sw fp32 per-row scales, bias fp32 (or NULL),
- * out bf16 (M x N).  v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulation.  N % 64 == 0, K % 64 == 0. */
-int csu_fp8_gemm(long M, int N, int K, const void* aq, const float* sa, const void* wq, const float* sw,
-                 const float* bias, void* out, void* stream);
-/* LayerNorm forward with an e4m3 output: yq = e4m3fn(LN(x) / s) (RNE), yscale[row] = s =
- * 2^ceil(log2(amax_row / 448)) (1 for an all-zero row; exact, as the weights': e4m3_row_scale); mean / rstd as
- * csu_layernorm_fwd. */
-int csu_layernorm_fwd_fp8(int rows, int C, float eps, int xdtype, const void* x, const float* gamma,
-                          const float* beta, void* yq, float* yscale, float* mean, float* rstd, void* stream);
-/* the same, also writing ydq (bf16, rows x C, or NULL) = e4m3fn(yq) * yscale[row] exactly: the
- * operand the weight gradient of the consuming Linear reads */
-int csu_layernorm_fwd_fp8_dq(int rows, int C, float eps, int xdtype, const void* x, const float* gamma,
-                             const float* beta, void* yq, float* yscale, void* ydq, float* mean, float* rstd,
-                             void* stream);
-/* out (bf16, rows x cols) = e4m3fn(q) * scale[row]; cols % 8 == 0 */
-int csu_dequant_e4m3_rows(long rows, int cols, const void* q, const float* scale, void* out, void* stream);
 /* e4m3 byte layouts of quantised weights (the fp8 fused Mlp's operand images): per item, src is a
  * rows x cols byte matrix; mode bit 0 = transpose (dst is cols x rows), bit 1 = permute the dst
  * columns inside every 64-column block: dst column 32h + 16t + 4g + i (h, t in {0,1}, g, i in 0..3)
