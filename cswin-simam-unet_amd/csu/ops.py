@@ -503,6 +503,7 @@ def _wgrad_post():
 
 
 def _wgrad_deferrable(dy2, wdt, bdt, params) -> bool:
+    _queue_flush()   # whatever the answer: the flush also resets the forward use counts (_USES)
     return (DEFER_WGRAD and dy2.dtype == torch.bfloat16 and bool(params) and wdt in (None, torch.float32)
             and bdt in (None, torch.float32) and _deferrable(*params))
 
@@ -548,8 +549,13 @@ class _LayerNormFn(torch.autograd.Function):
 def _ln_pre(x, weight, bias, eps, od):
     """The LayerNorm of x already computed by the fused Mlp that produced it (``_csu_ln``), or None."""
     pre = getattr(x, "_csu_ln", None)
-    if (pre is not None and pre[0] is weight and pre[1] is bias and pre[2] == float(eps) and pre[3].dtype == od
-            and pre[3].numel() == x.numel() and x.is_contiguous() and pre[6] == x._version):
+    if pre is None:
+        return None
+    if pre[6] != x._version:
+        del x._csu_ln    # x changed in place since the launch that computed it: stale for every later reader too
+        return None
+    if (pre[0] is weight and pre[1] is bias and pre[2] == float(eps) and pre[3].dtype == od
+            and pre[3].numel() == x.numel() and x.is_contiguous()):
         return pre
     return None
 
@@ -567,9 +573,18 @@ def _bf16_of(g: torch.Tensor) -> torch.Tensor:
     """bf16 copy of a gradient: the one a residual junction attached to it (csu_layernorm_bwd_ex
     writes it in the same pass), else a fresh cast."""
     b = getattr(g, "_csu_bf16", None)
-    if b is not None and b.shape == g.shape:
+    if b is not None and b.shape == g.shape and getattr(g, "_csu_bf16_v", None) == g._version:
         return b
     return g.reshape(g.shape).to(torch.bfloat16).contiguous()
+
+
+def attach_bf16(g: torch.Tensor, gb: torch.Tensor) -> torch.Tensor:
+    """Attach the bf16 copy ``gb`` of the gradient ``g`` for _bf16_of, with g's version counter: the
+    autograd engine sums a second gradient for the same tensor INTO g in place when g is singly
+    referenced (the Python attribute survives on it), after which the copy no longer equals g."""
+    g._csu_bf16 = gb
+    g._csu_bf16_v = g._version
+    return g
 
 
 class _LayerNormForkFn(torch.autograd.Function):
@@ -602,9 +617,7 @@ def _ln_fork_backward(ctx, x, w, mean, rstd, dres, dy):
     the LN parameters (``params``, ``pdtypes``).  ``dres`` None: the plain LayerNorm backward."""
     C = x.shape[-1]
     rows = x.numel() // C
-    if dy is None:
-        dy = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
-    dy = dy.contiguous()
+    dy = dy.contiguous()   # never None: no Function here turns gradient materialisation off
     if dy.dtype not in (torch.float32, torch.bfloat16):
         dy = dy.float()
     fp32 = x.dtype == torch.float32
@@ -630,7 +643,7 @@ def _ln_fork_backward(ctx, x, w, mean, rstd, dres, dy):
     if dres is not None and not fp32:    # non-fp32 residual stream: plain add (not on the bf16 path)
         dx = dx + dres.to(dx.dtype)
     if dxb is not None:
-        dx._csu_bf16 = dxb
+        attach_bf16(dx, dxb)
     return dx, dgb[:C].to(ctx.pdtypes[0]), dgb[C:].to(ctx.pdtypes[1])
 
 
@@ -802,6 +815,7 @@ class _CarafeHeadFoldedFn(torch.autograd.Function):
     def backward(ctx, dprob):
         x, enc, z, uf, prob, wo, bo, wh = ctx.saved_tensors
         B, H, W, C, s = ctx.geo
+        _queue_flush()   # the forward counted its parameters' uses (_USES): reset at the end of this backward
         dprob = dprob.float().contiguous()
         dx, denc = torch.empty_like(x), torch.empty_like(enc)
         du = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -896,6 +910,9 @@ def linear_wgrad(dy2: torch.Tensor, x2: torch.Tensor, out=None, work=None, defer
     (bf16): the reduction joins the end-of-backward batch (_wgrad_flush); the returned tensors are
     filled then -- only for gradients nothing reads earlier (see _wgrad_deferrable)."""
     require_device(dy2, x2)
+    # the kernels take row pitches N and K: a saved input that reached its Linear as a strided view
+    # (a slice of a wider buffer reshapes to rows with the buffer's pitch) is copied here
+    dy2, x2 = dy2.contiguous(), x2.contiguous()
     M, N = dy2.shape
     K = x2.shape[1]
     if dy2.dtype == torch.float32:
@@ -1080,6 +1097,10 @@ def _param_safe(p) -> bool:
     # LePE work -- the plain UNet -- would otherwise keep counting across steps, and from its second
     # step every conv weight would look shared and lose the side stream)
     _queue_flush()
+    # backward(create_graph=True): AccumulateGrad copies the incoming gradient on the launching stream
+    # instead of taking it (see _deferrable), i.e. while the side stream may still be writing it
+    if torch.is_grad_enabled():
+        return False
     p = _leaf(p)
     if p is None:
         return True
@@ -1092,6 +1113,7 @@ def _param_safe(p) -> bool:
 
 
 def _side_ok(t: torch.Tensor, *dtypes, params=()) -> bool:
+    _queue_flush()   # also with the side stream off: the flush resets the forward use counts (_USES)
     if not (SIDE_WGRAD and t.is_cuda) or any(d not in (None, torch.float32) for d in dtypes):
         return False
     if torch.cuda.is_current_stream_capturing() and not _SIDE_IN_GRAPH:
@@ -1247,7 +1269,8 @@ class _LinearFn(torch.autograd.Function):
         else:
             raise CsuError(f"linear: no csu GEMM for {cd} with in/out features {K}/{N} (bf16 needs multiples "
                            f"of 8, fp32 multiples of 4)")
-        ctx.save_for_backward(xc, wt if ctx.fast else wc)
+        # x2: the contiguous rows the GEMM read (xc itself unless x came as a strided view)
+        ctx.save_for_backward(x2.view(xc.shape), wt if ctx.fast else wc)
         ctx.meta = (x.dtype, weight.dtype, None if bias is None else bias.dtype)
         ctx.params = (weight, bias)
         _note_use(ctx, *ctx.params)
@@ -1311,8 +1334,7 @@ class _SharedCastFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g1, g2):
-        if g1 is None and g2 is None:
-            return None, None
+        # both present (an unused output's gradient is materialised as zeros)
         return grad_join(g1, g2, ctx.xdt), None
 
 
@@ -1341,8 +1363,7 @@ def grad_join(g1: Optional[torch.Tensor], g2: Optional[torch.Tensor], dtype: tor
     _launch("grad_join", lambda: lib().csu_grad_join(n, dtype_code(a), ptr(a), dtype_code(b) if b is not None else 0,
                                                      ptr(b), ptr(out), ptr(outb), stream_ptr(a.device)),
             n, n * (esize(a) + (esize(b) if b is not None else 0) + 6), prec="f32")
-    out._csu_bf16 = outb
-    return out
+    return attach_bf16(out, outb)
 
 
 class _BCELossFn(torch.autograd.Function):
@@ -2821,12 +2842,10 @@ class _LnLinearWsFn(torch.autograd.Function):
         wdt, bdt = ctx.lmeta
         C = x.shape[-1]
         rows = x.numel() // C
-        if dy is None:    # no gradient through the Linear: the plain fork backward
-            dx, dg, dbeta = _ln_fork_backward(ctx, x, g, mean, rstd, dres, None)
-            return dx, dg, dbeta, None, None, None, None, None, None
+        # dres / dy are never None (an unused output's gradient arrives as zeros: materialised)
         N = dy.shape[-1]
         dy2 = _bf16_of(dy).reshape(-1, N).contiguous()
-        dres_k = dres.float().contiguous() if dres is not None else None
+        dres_k = dres.float().contiguous()
         dx = torch.empty_like(x)
         dxb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
         nblk = rows // 64
@@ -2840,7 +2859,7 @@ class _LnLinearWsFn(torch.autograd.Function):
                 prec="bf16", tag=f"{rows}x{C}x{N}:lnbwd:ws")
         dg, dbeta = _ln_param_grads(ctx, rows, C, work, nblk)
         dw, db = _linear_param_grads(ctx.needs_input_grad[3:5], dy2, h, wdt, bdt, ctx.lin)
-        dx._csu_bf16 = dxb
+        attach_bf16(dx, dxb)
         return dx, dg, dbeta, dw, db, None, None, None, None
 
 
@@ -2922,7 +2941,7 @@ class _LnMlpResidualFn(torch.autograd.Function):
         dg, dbeta = _ln_param_grads(ctx, M, C, work, nblk)
         dw2, db2 = wgrad_maybe_side(dyb, gl, w2dt, b2dt, params=ctx.mlp[2:])
         dw1, db1 = wgrad_maybe_side(dh, h2, w1dt, b1dt, params=ctx.mlp[:2])
-        dx._csu_bf16 = dxb
+        attach_bf16(dx, dxb)
         return dx, dg, dbeta, None, dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None, None, None
 
 

@@ -79,14 +79,8 @@ class _SimAMForkFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g1, dy):
         x, stats = ctx.saved_tensors
-        if dy is None:
-            from .ops import grad_join
-            return grad_join(g1, None, torch.float32), None
-        if g1 is None or g1.dtype != torch.bfloat16:
-            dx = _SimAMFn.backward(ctx, dy)[0]
-            return (dx if g1 is None else dx + g1.float()), None
-        if dy.dtype not in (torch.float32, torch.bfloat16):
-            dy = dy.float()
+        # g1 and dy are both present and bf16: autograd materialises an unused output's gradient as
+        # zeros and casts every gradient to its output's dtype before it gets here
         dy, g1 = dy.contiguous(), g1.contiguous()
         B, L, C = x.shape
         dx = torch.empty_like(x)
@@ -97,8 +91,8 @@ class _SimAMForkFn(torch.autograd.Function):
         launch("simam_bwd", lambda: Lb.csu_simam_bwd_join(B, L, C, ptr(x), ptr(stats), dtype_code(dy), ptr(dy), ptr(g1),
                                                           ptr(dx), ptr(dxb), ptr(work), n, stream_ptr(x.device)),
                30 * x.numel(), x.numel() * (3 * 4 + 2 * dy.element_size() + 2 + 4 + 2), prec="f32")
-        dx._csu_bf16 = dxb
-        return dx, None
+        from .ops import attach_bf16
+        return attach_bf16(dx, dxb), None
 
 
 def simam_fork(x: torch.Tensor, lam: float = 1e-4):
