@@ -35,6 +35,13 @@
 //   + w_bd[0] BD,  BD = sum over live pixels and c in Cb of p_c phi_c / (n |Cb|),  n = sum_c T_c,  Cb = 1 .. K-1 or all;
 //   phi dense fp32 (B, K, HW) read per class plane; one more partial sum per item (index 2 + 5 K); ce_finish leaves
 //   1 / (n |Cb|) behind 1 / sum w; backward adds g w_bd / (n |Cb|) p_k (phi_k [k in Cb] - sum_{c in Cb} phi_c p_c).
+// Hard-example CE (csu_seg_hard_*, template flag HD; off in the other two families, whose arithmetic it leaves alone):
+//   l = w[t] u^gamma L per live pixel, u = sum_{k != t} p_k, L = log(sum) + (max - z_t), in the place of w[t] L.  Without
+//   a selection nothing else changes.  With one (rho on the device), ce_partial also stores every l as an fp32 key,
+//   csu_kth_largest (kth_largest.hip) finds tau = the k-th largest, hd_msum sums l and w[t] above tau and w[t] at tau per
+//   item in a fixed order, ce_finish forms HCE = (S_gt + (k - n_gt) tau) / (W_gt + f W_eq), f = (k - n_gt) / n_eq, in
+//   fp64 and leaves 1 / W, tau, f in coef; backward scales the CE part by m (u^gamma + gamma q u^(gamma - 1) L) with
+//   m = 1, f, 0 from the stored key against tau.
 // No label ever indexes memory (class weight and z_t are selected by comparison), so a label
 // outside [0, K) cannot fault; it matches no class.  The summation order is a function of the
 // shape, the strides and the address mod 16 only.
@@ -84,6 +91,41 @@ struct BdArgs {
     const float* w_bd;   // one float on the device
     int bg;
 };
+
+// The hard-example CE term (csu_seg_hard_*): l = w[t] u^gamma L per live pixel, u = sum_{k != t} p_k, L = the pixel's
+// CE.  keys == nullptr: HCE = sum l / sum w.  Otherwise the forward leaves every l in keys (a dead pixel: HD_DEAD,
+// sign bit set), csu_kth_largest leaves (tau, n_gt, n_eq, k, n) in sel, and the pixels above tau count in full,
+// those equal to it with f = (k - n_gt) / n_eq.  Keys are compared as bit patterns, which order non-negative floats.
+struct HdArgs {
+    float gamma;
+    float* keys;         // (B, HW) fp32, or nullptr
+    const double* sel;   // csu_kth_largest's five values
+    float* msum;         // per item: sum of l above tau, sum of w above tau, sum of w at tau
+};
+constexpr float HD_DEAD = -1.f;
+
+// u^gamma; 1 when gamma = 0, also at u = 0.  gamma is uniform: the usual exponents 1 and 2 skip powf, which
+// measured 75 us of the 200 us of forward + backward at B 16, K 5, 512 x 512 (profiles/hard_example_loss_timing.txt)
+__device__ __forceinline__ float hd_pow(float u, float gamma) {
+    return gamma == 0.f ? 1.f : gamma == 1.f ? u : gamma == 2.f ? u * u : powf(u, gamma);
+}
+// l of one pixel, >= +0 (a NaN stays one): L = log(sum) + (max - z_t) >= 0 by construction (in that association it
+// keeps its precision next to logits of 1e4, which the gradient, unlike plain CE's, needs), and -0 is flushed
+__device__ __forceinline__ float hd_term(float wt, float u, float L, float gamma) {
+    const float l = wt * hd_pow(u, gamma) * L;
+    return l == 0.f ? 0.f : l;
+}
+// d l / d L at fixed weights of the softmax: u^gamma + gamma q u^(gamma - 1) L, the second summand 0 at gamma = 0,
+// u = 0 or L = 0 (where u^(gamma - 1) may be infinite)
+__device__ __forceinline__ float hd_factor(float q, float u, float L, float gamma) {
+    const float second = gamma != 0.f && u > 0.f && L > 0.f ? gamma * q * hd_pow(u, gamma - 1.f) * L : 0.f;
+    return hd_pow(u, gamma) + second;
+}
+// the weight m of a pixel's key in the selection
+__device__ __forceinline__ float hd_select(float key, float tau, float f) {
+    const unsigned kb = __float_as_uint(key), tb = __float_as_uint(tau);
+    return (int)kb < 0 || kb < tb ? 0.f : kb > tb ? 1.f : f;
+}
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -231,8 +273,9 @@ __device__ __forceinline__ void item_range(const CeArgs& a, long it, bool vec_ok
 }
 
 // BD: one more sum per item, the boundary term's sum of p_c phi_c, at index 2 + 5 K
-template <typename T, int KB, int MODE, bool BD>
-__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, int vec_ok, float* __restrict__ partial) {
+// HD: the CE numerator is the sum of l = w[t] u^gamma L, and with hd.keys every pixel's l goes there as its key
+template <typename T, int KB, int MODE, bool BD, bool HD>
+__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, HdArgs hd, int vec_ok, float* __restrict__ partial) {
     constexpr int V = ce_vec(KB, MODE);
     constexpr bool LANE_CNT = KB >= 16;
     constexpr int NC = LANE_CNT ? 1 : KB;
@@ -279,7 +322,16 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, int vec_ok
                 float m, s;
                 int arg;
                 softmax_px<KB>(z[j], m, s, arg);
-                ce += live ? wt * ((logf(s) + m) - zt) : 0.f;
+                if constexpr (HD) {
+                    float u = 0.f;
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) u += t == k ? 0.f : z[j][k];
+                    const float l = hd_term(wt, u, logf(s) + (m - zt), hd.gamma);
+                    ce += t >= 0 ? l : 0.f;
+                    if (hd.keys && e0 + j >= lo && e0 + j < hi) hd.keys[b * a.HW + e0 + j] = t >= 0 ? l : HD_DEAD;
+                } else {
+                    ce += live ? wt * ((logf(s) + m) - zt) : 0.f;
+                }
                 sw += wt;
                 const int pred = live ? arg : -1;
 #pragma unroll
@@ -337,13 +389,15 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, int vec_ok
 }
 
 // coef: rows x K x 2 floats (A, C), then 1 / sum w; BD: then 1 / (n |Cb|), and terms = {the loss without the
-// boundary term, BD}
-template <bool BD>
+// boundary term, BD}.  HD: HCE in the place of CE; coef: (A, C), then 1 / W (W = HCE's denominator), tau, f (0, 1
+// without a selection), and hterms = fp64 {HCE, the Tversky term, tau, k} (k = n without a selection)
+template <bool BD, bool HD>
 __global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows, const float* __restrict__ partial,
                                                 float w_ce, float w_tv, float alpha, float beta, float smooth, int bg,
-                                                BdArgs bd, float* __restrict__ terms, float* __restrict__ loss,
-                                                double* __restrict__ stats, float* __restrict__ coef) {
-    __shared__ double red[BD ? 5 : 3][NT / 64];
+                                                BdArgs bd, HdArgs hd, float* __restrict__ terms, double* __restrict__ hterms,
+                                                float* __restrict__ loss, double* __restrict__ stats,
+                                                float* __restrict__ coef) {
+    __shared__ double red[HD ? 7 : BD ? 5 : 3][NT / 64];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ns = 2 + 5 * K + (BD ? 1 : 0);
     const long items = (long)B * cpi;
@@ -415,13 +469,57 @@ __global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows,
             red[4][w] = bs;
         }
     }
+    if constexpr (HD) {
+        double sg = 0., wg = 0., we = 0., n = 0.;   // n: as for BD
+        for (long i = threadIdx.x; i < items; i += NT) {
+            const float* q = partial + i * ns + 2 + 2 * K;
+            for (int c = 0; c < K; ++c) n += (double)q[c];
+            if (hd.keys) {
+                sg += (double)hd.msum[3 * i];
+                wg += (double)hd.msum[3 * i + 1];
+                we += (double)hd.msum[3 * i + 2];
+            }
+        }
+        sg = wave_sum_d(sg);
+        wg = wave_sum_d(wg);
+        we = wave_sum_d(we);
+        n = wave_sum_d(n);
+        if (lane == 0) {
+            red[3][w] = sg;
+            red[4][w] = wg;
+            red[5][w] = we;
+            red[6][w] = n;
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double tot[BD ? 5 : 3];
+        double tot[HD ? 7 : BD ? 5 : 3];
 #pragma unroll
-        for (int k = 0; k < (BD ? 5 : 3); ++k) tot[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-        const double isw = tot[2] > 0. ? 1.0 / tot[2] : 0.;
+        for (int k = 0; k < (HD ? 7 : BD ? 5 : 3); ++k) tot[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
         const int nc = bg ? K : K - 1;
+        if constexpr (HD) {
+            double num = tot[1], W = tot[2], tau = 0., f = 1., k = tot[6];
+            if (hd.keys) {   // sum m l = sum above tau + (k - n_gt) tau;  sum m w = sum above tau + f (sum at tau)
+                tau = hd.sel[0];
+                k = hd.sel[3];
+                const double rest = k - hd.sel[1];
+                f = hd.sel[2] > 0. ? rest / hd.sel[2] : 0.;
+                num = tot[3] + (rest > 0. ? rest * tau : 0.);
+                W = tot[4] + f * tot[5];
+            }
+            const double iw = W > 0. ? 1.0 / W : 0., hce = W > 0. ? num * iw : 0.;
+            const double tv = tot[0] / ((double)rows * nc);
+            coef[2 * (long)rows * K] = (float)iw;
+            coef[2 * (long)rows * K + 1] = (float)tau;
+            coef[2 * (long)rows * K + 2] = (float)f;
+            hterms[0] = hce;
+            hterms[1] = tv;
+            hterms[2] = tau;
+            hterms[3] = k;
+            loss[0] = (float)((double)w_ce * hce + (double)w_tv * tv);
+            return;
+        }
+        const double isw = tot[2] > 0. ? 1.0 / tot[2] : 0.;
         const double base = (double)w_ce * tot[1] * isw + (double)w_tv * tot[0] / ((double)rows * nc);
         coef[2 * (long)rows * K] = (float)isw;
         if constexpr (BD) {
@@ -442,10 +540,13 @@ __global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows,
 // term when it is switched off (w_bd[0] = 0, or a zero upstream gradient), so that phi is not read and the
 // gradient is csu_seg_ce_bwd's bit for bit.  One kernel with the term in the same expression does not give that:
 // the compiler contracts and packs the multiplies and adds of the whole expression as it sees fit.
-template <typename T, int KB, int MODE, bool BD>
-__global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, int vec_ok, int rows, const float* __restrict__ dloss,
-                                                  const float* __restrict__ coef, float w_ce, float tv_scale,
-                                                  T* __restrict__ dz) {
+// HD: the CE part of dz_k becomes g w_ce m w[t] (p_k - [k = t]) (u^gamma + gamma q u^(gamma - 1) L) / W.  m comes from
+// the pixel's stored key against tau, never from l formed again here: this kernel's l need not round as the
+// forward's did, and a key that moved across tau would move the gradient by a whole pixel's worth.
+template <typename T, int KB, int MODE, bool BD, bool HD>
+__global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, HdArgs hd, int vec_ok, int rows,
+                                                  const float* __restrict__ dloss, const float* __restrict__ coef, float w_ce,
+                                                  float tv_scale, T* __restrict__ dz) {
     constexpr int V = ce_vec(KB, MODE);
     const int K = a.K;
     if (bd.w_bd != nullptr) {
@@ -455,6 +556,11 @@ __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, int vec_o
     const float g = dloss[0], g1 = g * w_ce * coef[2 * (long)rows * K], g2 = g * tv_scale;
     float g3 = 0.f;
     if constexpr (BD) g3 = g * bd.w_bd[0] * coef[2 * (long)rows * K + 1];
+    float tau = 0.f, ftie = 1.f;
+    if constexpr (HD) {
+        tau = coef[2 * (long)rows * K + 1];
+        ftie = coef[2 * (long)rows * K + 2];
+    }
     float cw[KB];
 #pragma unroll
     for (int k = 0; k < KB; ++k) cw[k] = (a.cw && k < K) ? a.cw[k] : 1.f;
@@ -485,13 +591,29 @@ __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, int vec_o
                 float wt = 0.f;
 #pragma unroll
                 for (int k = 0; k < KB; ++k) wt = t == k ? cw[k] : wt;
+                float zt = 0.f;
+                if constexpr (HD) {
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) zt = t == k ? z[j][k] : zt;
+                }
                 float m, s;
                 int arg;
                 softmax_px<KB>(z[j], m, s, arg);
                 float dot = 0.f;
 #pragma unroll
                 for (int k = 0; k < KB; ++k) dot += ((t == k ? A[k] : 0.f) - C[k]) * z[j][k];
-                const float c1 = g1 * wt;
+                float hf = 1.f;
+                if constexpr (HD) {
+                    float q = 0.f, u = 0.f;
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) {
+                        q = t == k ? z[j][k] : q;
+                        u += t == k ? 0.f : z[j][k];
+                    }
+                    hf = hd_factor(q, u, logf(s) + (m - zt), hd.gamma);
+                    if (hd.keys) hf *= t >= 0 ? hd_select(hd.keys[b * a.HW + e0 + j], tau, ftie) : 0.f;
+                }
+                const float c1 = HD ? g1 * wt * hf : g1 * wt;
                 float fdot = 0.f;
                 if constexpr (BD) {
 #pragma unroll
@@ -539,6 +661,50 @@ __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, int vec_o
                 }
             }
         }
+    }
+}
+
+// The selected sums of the hard-example term, per item in a fixed order: over the item's keys above tau the sum of
+// l and of w[t], over those equal to tau the sum of w[t].  Reads the keys, and the labels only when there are class
+// weights (without them w = 1 on every live key).
+__global__ __launch_bounds__(NT) void hd_msum(CeArgs a, HdArgs hd) {
+    __shared__ float red[NT / 64][3];
+    const int K = a.K, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned tb = __float_as_uint((float)hd.sel[0]);
+    float cw[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) cw[k] = (a.cw && k < K) ? a.cw[k] : 1.f;
+    for (long it = blockIdx.x; it < a.items; it += gridDim.x) {
+        const long b = it / a.cpi, lo = (it - b * a.cpi) * a.clen, hi = min(lo + a.clen, a.HW);
+        float sg = 0.f, wg = 0.f, we = 0.f;
+        for (long e = lo + threadIdx.x; e < hi; e += NT) {
+            const float l = hd.keys[b * a.HW + e];
+            const unsigned kb = __float_as_uint(l);
+            float wt = 1.f;
+            if (a.cw) {
+                bool live;
+                const int t = load_label(a, b, e, lo, hi, live);
+                wt = 0.f;
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k) wt = t == k ? cw[k] : wt;
+            }
+            const bool on = (int)kb >= 0;
+            sg += on && kb > tb ? l : 0.f;
+            wg += on && kb > tb ? wt : 0.f;
+            we += on && kb == tb ? wt : 0.f;
+        }
+        sg = wave_sum(sg);
+        wg = wave_sum(wg);
+        we = wave_sum(we);
+        if (lane == 0) {
+            red[wv][0] = sg;
+            red[wv][1] = wg;
+            red[wv][2] = we;
+        }
+        __syncthreads();
+        if (threadIdx.x < 3)
+            hd.msum[3 * it + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        __syncthreads();
     }
 }
 
@@ -602,11 +768,21 @@ CeArgs ce_pack(int B, int K, long HW, const void* z, long s_b, long s_k, long s_
     return a;
 }
 
-// the two forward launches and the backward launch, shared by csu_seg_ce_* (BD = false) and csu_seg_bd_*
-template <bool BD>
+// what the host needs for the selection of the hard-example term (hd.keys set): rho, and csu_kth_largest's workspace
+struct HdSelect {
+    const float* rho;
+    double* hterms;
+    void* kth_ws;
+    size_t kth_bytes;
+};
+
+// the two forward launches and the backward launch, shared by csu_seg_ce_* (BD = false), csu_seg_bd_* and
+// csu_seg_hard_* (HD; with keys the selection and its sums run between the two)
+template <bool BD, bool HD = false>
 int ce_forward(const char* what, const CeArgs& a, const BdArgs& bd, int rows, int dtype, int pad_ok, float w_ce, float w_tv,
                float alpha, float beta, float smooth, int include_background, float* terms, float* loss, double* stats,
-               float* coef, void* workspace, void* stream) {
+               float* coef, void* workspace, void* stream, const HdArgs& hd = HdArgs{0.f, nullptr, nullptr, nullptr},
+               const HdSelect& hs = HdSelect{nullptr, nullptr, nullptr, 0}) {
     const int K = a.K, KB = ce_bucket(K);
     const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
     hipStream_t st = as_stream(stream);
@@ -617,19 +793,30 @@ int ce_forward(const char* what, const CeArgs& a, const BdArgs& bd, int rows, in
         using T = std::conditional_t<decltype(f32)::value, float, bf16>;
         with_bucket(KB, [&](auto kb) {
             with_mode(mode, [&](auto md) {
-                ce_partial<T, decltype(kb)::value, decltype(md)::value, BD><<<nb, NT, 0, st>>>(a, bd, vec_ok, (float*)workspace);
+                ce_partial<T, decltype(kb)::value, decltype(md)::value, BD, HD>
+                    <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, (float*)workspace);
             });
         });
     });
     if (int e = check_launch(what)) return e;
-    ce_finish<BD><<<1, NT, 0, st>>>(a.B, K, a.cpi, rows, (const float*)workspace, w_ce, w_tv, alpha, beta, smooth,
-                                    include_background != 0, bd, terms, loss, stats, coef);
+    if constexpr (HD) {
+        if (hd.keys) {
+            if (int e = csu_kth_largest((long)a.B * a.HW, hd.keys, hs.rho, const_cast<double*>(hd.sel), hs.kth_ws, hs.kth_bytes,
+                                        stream))
+                return e;
+            hd_msum<<<nb, NT, 0, st>>>(a, hd);
+            if (int e = check_launch(what)) return e;
+        }
+    }
+    ce_finish<BD, HD><<<1, NT, 0, st>>>(a.B, K, a.cpi, rows, (const float*)workspace, w_ce, w_tv, alpha, beta, smooth,
+                                        include_background != 0, bd, hd, terms, hs.hterms, loss, stats, coef);
     return check_launch(what);
 }
 
-template <bool BD>
+template <bool BD, bool HD = false>
 int ce_backward_launch(const char* what, const CeArgs& a, const BdArgs& bd, int rows, int dtype, int pad_ok, float w_ce,
-                       float w_tv, int include_background, const float* dloss, const float* coef, void* dz, void* stream) {
+                       float w_tv, int include_background, const float* dloss, const float* coef, void* dz, void* stream,
+                       const HdArgs& hd = HdArgs{0.f, nullptr, nullptr, nullptr}) {
     const int K = a.K, KB = ce_bucket(K);
     const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
     hipStream_t st = as_stream(stream);
@@ -642,10 +829,10 @@ int ce_backward_launch(const char* what, const CeArgs& a, const BdArgs& bd, int 
         with_bucket(KB, [&](auto kb) {
             with_mode(mode, [&](auto md) {
                 if constexpr (BD)   // the gated pair: see ce_backward
-                    ce_backward<T, decltype(kb)::value, decltype(md)::value, false>
-                        <<<nb, NT, 0, st>>>(a, bd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
-                ce_backward<T, decltype(kb)::value, decltype(md)::value, BD>
-                    <<<nb, NT, 0, st>>>(a, bd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
+                    ce_backward<T, decltype(kb)::value, decltype(md)::value, false, false>
+                        <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
+                ce_backward<T, decltype(kb)::value, decltype(md)::value, BD, HD>
+                    <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
             });
         });
     });
@@ -719,4 +906,64 @@ extern "C" int csu_seg_bd_bwd(int B, int K, long HW, int rows, int dtype, const 
     const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
     return ce_backward_launch<true>("seg_bd_bwd", a, BdArgs{phi, w_bd, bd_background != 0}, rows, dtype, pad_ok, w_ce, w_tversky,
                                     include_background, dloss, coef, dz, stream);
+}
+
+// ---- the same loss with the hard-example CE term: focal weighting and / or a top-k selection --------
+namespace csu {
+namespace {
+// workspace: csu_kth_largest's, its five doubles, then the (2 + 5 K) partial sums and the 3 selected sums per item
+struct HdLayout {
+    size_t kth, sel, partial, msum, total;
+};
+HdLayout hd_layout(int B, int K, long HW) {
+    HdLayout l;
+    const size_t items = (size_t)ce_plan(B, HW).items;
+    l.kth = csu_kth_largest_workspace((long)B * HW);
+    l.sel = l.kth;
+    l.partial = l.sel + 6 * sizeof(double);
+    l.msum = l.partial + items * ce_nsum(K) * sizeof(float);
+    l.total = (l.msum + items * 3 * sizeof(float) + 7) & ~(size_t)7;
+    return l;
+}
+}  // namespace
+}  // namespace csu
+
+extern "C" size_t csu_seg_hard_workspace(int B, int K, long HW) {
+    if (B < 1 || HW < 1 || K < 2 || K > KMAX) return 0;
+    return hd_layout(B, K, HW).total;
+}
+
+extern "C" int csu_seg_hard_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                                int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                                float w_ce, float w_tversky, float alpha, float beta, float smooth, int include_background,
+                                float gamma, const float* rho, float* keys, float* loss, double* terms, double* stats,
+                                float* coef, void* workspace, size_t ws_bytes, void* stream) {
+    if (int e = ce_args("seg_hard_fwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky)) return e;
+    if (!(alpha >= 0.f) || !(beta >= 0.f)) return fail(CSU_E_ARG, "seg_hard_fwd: alpha and beta must be >= 0");
+    if (!(smooth > 0.f)) return fail(CSU_E_ARG, "seg_hard_fwd: smooth must be > 0");
+    if (!(gamma >= 0.f) || gamma == INFINITY) return fail(CSU_E_ARG, "seg_hard_fwd: gamma must be finite and >= 0");
+    if (!z || !t || !loss || !coef || !terms) return fail(CSU_E_ARG, "seg_hard_fwd: null z, t, loss, terms or coef");
+    if ((rho != nullptr) != (keys != nullptr)) return fail(CSU_E_ARG, "seg_hard_fwd: rho and keys go together");
+    if (!workspace || ((uintptr_t)workspace & 7) || ws_bytes < csu_seg_hard_workspace(B, K, HW))
+        return fail(CSU_E_WORKSPACE, "seg_hard_fwd: workspace (8-byte aligned)");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    const HdLayout l = hd_layout(B, K, HW);
+    char* ws = (char*)workspace;
+    const HdArgs hd{gamma, keys, (const double*)(ws + l.sel), (float*)(ws + l.msum)};
+    return ce_forward<false, true>("seg_hard_fwd", a, BdArgs{nullptr, nullptr, 0}, rows, dtype, pad_ok, w_ce, w_tversky, alpha,
+                                   beta, smooth, include_background, nullptr, loss, stats, coef, ws + l.partial, stream, hd,
+                                   HdSelect{rho, terms, ws, l.kth});
+}
+
+extern "C" int csu_seg_hard_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                                int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                                const float* dloss, const float* coef, float w_ce, float w_tversky, int include_background,
+                                float gamma, const float* keys, void* dz, void* stream) {
+    if (int e = ce_args("seg_hard_bwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky)) return e;
+    if (!(gamma >= 0.f) || gamma == INFINITY) return fail(CSU_E_ARG, "seg_hard_bwd: gamma must be finite and >= 0");
+    if (!z || !t || !dloss || !coef || !dz) return fail(CSU_E_ARG, "seg_hard_bwd: null z, t, dloss, coef or dz");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    return ce_backward_launch<false, true>("seg_hard_bwd", a, BdArgs{nullptr, nullptr, 0}, rows, dtype, pad_ok, w_ce, w_tversky,
+                                           include_background, dloss, coef, dz, stream,
+                                           HdArgs{gamma, const_cast<float*>(keys), nullptr, nullptr});
 }

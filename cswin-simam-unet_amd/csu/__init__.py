@@ -12,7 +12,8 @@ from .unet import DoubleConv, Down, UNet, Up
 from .train import (bce_loss, dice_coefficient, evaluate_model, iou_score, make_optimizer, make_scheduler,
                     train_model, train_step)
 from .losses import (BoundarySegLoss, MultiClassSegLoss, SegLoss, bce_dice_loss, boundary_loss, ce_dice_boundary_loss,
-                     ce_dice_loss, ce_loss, dice_loss, linear_ramp, multiclass_dice_loss, tversky_loss)
+                     ce_dice_loss, ce_loss, dice_loss, linear_ramp, multiclass_dice_loss, tversky_loss,
+                     HardExampleSegLoss, dice_focal_loss, dice_topk_loss, focal_loss, topk_ce_loss)
 from .optim import FusedAdam, FusedAdamW
 from .ema import WeightEMA
 from .infer import (SlidingWindowPredictor, evaluate_full_res, plan_axis, plan_tiles, reference_predict, window_1d)
@@ -35,4 +36,5 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "reference_distance_transform_edt", "connected_components", "postprocess_labels", "PostProcess",
            "reference_connected_components", "reference_postprocess_labels", "SpatialAugment", "reference_augment",
            "BoundarySegLoss", "boundary_loss", "ce_dice_boundary_loss", "linear_ramp", "signed_distance_map",
-           "reference_signed_distance_map"]
+           "reference_signed_distance_map", "HardExampleSegLoss", "focal_loss", "dice_focal_loss", "topk_ce_loss",
+           "dice_topk_loss"]

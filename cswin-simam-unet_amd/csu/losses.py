@@ -1,6 +1,7 @@
 """Training criteria beyond nn.BCELoss: soft Dice, BCE + Dice, Tversky (binary, ``SegLoss``) and softmax
-cross-entropy + per-class Dice / Tversky on integer label maps (``MultiClassSegLoss``), and that with the boundary
-loss of signed distance maps on top (``BoundarySegLoss``, at the end).
+cross-entropy + per-class Dice / Tversky on integer label maps (``MultiClassSegLoss``), that with the boundary
+loss of signed distance maps on top (``BoundarySegLoss``), and that with a focal or top-k cross-entropy in the
+place of the plain one (``HardExampleSegLoss``, at the end).
 
 One family, ``SegLoss``:  ``bce * BCE + tversky * mean_r(1 - TI_r)`` on probabilities ``p`` and
 targets ``t`` viewed as rows (one row for the whole batch, or one per image), with
@@ -187,6 +188,11 @@ class MultiClassSegLoss:
 
     def _torch(self, z, t):
         """The same formula in torch ops, in z's floating dtype: z (B, K, *), t (B, *) int64."""
+        ce, tv = self._terms_torch(z, t)
+        return self.ce * ce + self.tversky * tv
+
+    def _terms_torch(self, z, t):
+        """(CE, mean_r mean_{c in C} (1 - TI_rc)) of _torch."""
         B, K = z.shape[0], z.shape[1]
         rows = B if self.per_sample else 1
         z2 = z.reshape(B, K, -1)
@@ -213,7 +219,7 @@ class MultiClassSegLoss:
         one_minus = 1.0 - (tp + self.smooth) / den
         if not self.include_background:
             one_minus = one_minus[:, 1:]
-        return self.ce * ce + self.tversky * one_minus.mean()
+        return ce, one_minus.mean()
 
     def hard_stats(self, z, t):
         """fp64 (3, K) [I; Pr; T] in torch ops; the first maximum is the prediction."""
@@ -446,3 +452,182 @@ def ce_dice_boundary_loss(num_classes: int, ce: float = 1.0, dice: float = 1.0, 
                            class_weight=class_weight, ignore_index=ignore_index, per_sample=per_sample,
                            include_background=include_background, boundary=boundary,
                            boundary_background=boundary_background, spacing=spacing, clip=clip, schedule=schedule)
+
+
+class HardExampleSegLoss(MultiClassSegLoss):
+    """``MultiClassSegLoss`` whose CE term weighs the pixels by how hard they are: the focal loss (Lin et al. 2017,
+    ``gamma``), the top-k / OHEM cross-entropy over the batch (nnU-Net's ``TopKLoss``, ``top_k``), or both.  For a
+    live pixel i (label t in [0, K), not ``ignore_index``) with p = softmax(z_i):
+
+        q = p_t,   u = sum_{k != t} p_k  (1 - q without its cancellation),   L = logsumexp(z_i) - z_{i,t},
+        l_i = w[t] u^gamma L                                                  (u^gamma = 1 at gamma = 0; l_i >= +0),
+        n = the live pixels of the batch,
+        top_k = None:  HCE = sum_i l_i / sum_i w[t_i]                         (0 when the denominator is 0),
+        top_k = rho:   k = max(1, floor(double(float32(rho)) n)),  tau = the k-th largest l_i (as fp32 values),
+                       n_gt = #{l_i > tau},  n_eq = #{l_i = tau},  f = (k - n_gt) / n_eq,
+                       m_i = 1 (l_i > tau), f (l_i = tau), 0 (l_i < tau),
+                       HCE = sum_i m_i l_i / sum_i m_i w[t_i]                 (0 when the denominator is 0; n = 0: 0),
+        loss = ce * HCE + tversky * mean_r mean_{c in C} (1 - TI_rc).
+
+    The values tied at the threshold share the remaining places equally, so the loss does not depend on the order
+    of the pixels and the gradient, dHCE/dz_{i,k} = m_i w[t] (p_k - [k = t]) (u^gamma + gamma q u^(gamma-1) L) / W
+    with W the denominator of HCE, is one definite subgradient.  ``top_k = 1.0`` is ``top_k = None``;
+    ``gamma = 0, top_k = None`` is ``MultiClassSegLoss``; with unit weights, nothing ignored and rho n an integer,
+    ``gamma = 0, top_k = rho`` is ``torch.topk(F.cross_entropy(z, t, reduction="none").view(-1), k).values.mean()``.
+    The Tversky term and every other argument are ``MultiClassSegLoss``'; ``per_sample`` concerns that term only.
+
+    ``gamma`` is a host constant.  The fraction lives in a one-element device tensor the kernels read:
+    ``set_top_k(rho)`` fills it in place, so a captured graph follows a schedule without a re-capture; ``top_k`` is
+    the host copy (None: no selection, and that cannot be changed later).  ``schedule``: a callable epoch -> rho,
+    applied by ``on_epoch(epoch)``, which csu.train.train_model calls at the start of every epoch.  ``last_terms``:
+    the fp64 (4,) device tensor (HCE, Tversky term, tau, k) of the last call (no selection: tau = 0, k = n).
+
+    On the GPU with K <= 32 everything comes from the fused csu_seg_hard kernels, the selection from
+    csu_kth_largest, with no host synchronisation; CPU tensors and more classes take the same formula, tie rule
+    included, in torch ops."""
+
+    def __init__(self, num_classes: int, ce: float = 1.0, tversky: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
+                 smooth: float = 0.5, class_weight=None, ignore_index: int = -100, per_sample: bool = False,
+                 include_background: bool = True, gamma: float = 0.0, top_k=None, schedule=None):
+        super().__init__(num_classes, ce, tversky, alpha, beta, smooth, class_weight, ignore_index, per_sample,
+                         include_background)
+        if not float(gamma) >= 0.0 or float(gamma) == float("inf"):
+            raise ValueError(f"HardExampleSegLoss: gamma must be a finite number >= 0 (got {gamma!r})")
+        if top_k is not None:
+            self._check_top_k(top_k)
+        if schedule is not None and not callable(schedule):
+            raise ValueError("HardExampleSegLoss: schedule is a callable epoch -> top_k fraction, or None")
+        if schedule is not None and top_k is None:
+            raise ValueError("HardExampleSegLoss: a schedule needs a top_k to start from")
+        self.gamma, self.schedule = float(gamma), schedule
+        self._rho, self._rhos = None if top_k is None else float(top_k), {}
+        self.last_terms = None
+
+    @staticmethod
+    def _check_top_k(rho):
+        if isinstance(rho, bool) or not 0.0 < float(rho) <= 1.0:
+            raise ValueError(f"HardExampleSegLoss: top_k must be a fraction in (0, 1], or None (got {rho!r})")
+
+    def __repr__(self):
+        return (f"HardExampleSegLoss({super().__repr__()[len('MultiClassSegLoss('):-1]}, gamma={self.gamma}, "
+                f"top_k={self._rho}, schedule={self.schedule!r})")
+
+    @property
+    def top_k(self):
+        """The current top-k fraction (the host copy of the device scalar), or None."""
+        return self._rho
+
+    def set_top_k(self, rho: float) -> None:
+        """Set the fraction; every device's scalar is filled in place (no re-capture, no synchronisation)."""
+        if self._rho is None:
+            raise ValueError("HardExampleSegLoss: this criterion was made without a selection (top_k=None)")
+        self._check_top_k(rho)
+        self._rho = float(rho)
+        for t in self._rhos.values():
+            t.fill_(self._rho)
+
+    def on_epoch(self, epoch: int) -> None:
+        """Apply the schedule, if there is one, for the epoch that starts (0-based)."""
+        if self.schedule is not None:
+            self.set_top_k(self.schedule(int(epoch)))
+
+    def _scalar(self, device):
+        if self._rho is None:
+            return None
+        t = self._rhos.get(device)
+        if t is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HardExampleSegLoss: call the criterion once on this device before capturing it in a "
+                                   "graph (the fraction's device scalar is made at the first call)")
+            t = self._rhos[device] = torch.full((1,), self._rho, dtype=torch.float32, device=device)
+        return t
+
+    def _hard_torch(self, z, t, rho):
+        """(HCE, tau, k) in torch ops, in z's floating dtype: z (B, K, *), t (B, *) int64, rho a one-element fp32
+        tensor or None."""
+        B, K = z.shape[0], z.shape[1]
+        z2, t2 = z.reshape(B, K, -1), t.reshape(B, -1)
+        live = (t2 != self.ignore_index) & (t2 >= 0) & (t2 < K)
+        tc = torch.where(live, t2, torch.zeros_like(t2))
+        w = self._weight(z.device)
+        w = torch.ones(K, dtype=z.dtype, device=z.device) if w is None else w.to(z.dtype)
+        lv = live.to(z.dtype)
+        lsm = torch.log_softmax(z2, 1)
+        oh = F.one_hot(tc, K).permute(0, 2, 1).to(z.dtype)
+        L = -lsm.gather(1, tc.unsqueeze(1)).squeeze(1)
+        wt = w[tc] * lv
+        if self.gamma == 0.0:
+            ug = torch.ones_like(L)
+        else:
+            u = (lsm.exp() * (1.0 - oh)).sum(1)
+            pos = u > 0            # u^gamma and its derivative are 0 at u = 0, whatever gamma > 0
+            ug = torch.where(pos, torch.where(pos, u, torch.ones_like(u)).pow(self.gamma), torch.zeros_like(u))
+        l = wt * ug * L
+        n = live.sum()
+        if rho is None:
+            num, W, tau, k = l.sum(), wt.sum(), torch.zeros((), dtype=z.dtype, device=z.device), n.to(torch.float64)
+        else:
+            kk = torch.floor(rho[0].double() * n.double()).clamp(min=1.0).minimum(n.double())      # 0 when n = 0
+            keys = torch.where(live, l.detach(), torch.full_like(l, -1.0)).reshape(-1)
+            srt = torch.sort(keys, descending=True).values
+            tau = srt[(kk.long() - 1).clamp(min=0)].clamp_min(0.0)
+            gt, eq = live.reshape(-1) & (keys > tau), live.reshape(-1) & (keys == tau)
+            n_gt, n_eq = gt.sum().double(), eq.sum().double()
+            f = torch.where(n_eq > 0, (kk - n_gt) / n_eq.clamp(min=1.0), torch.zeros_like(kk))
+            m = (gt.to(torch.float64) + f * eq.to(torch.float64)).to(z.dtype).reshape(l.shape)
+            num, W, k = (m * l).sum(), (m * wt).sum(), kk
+        hce = torch.where(W > 0, num / torch.where(W > 0, W, torch.ones_like(W)), num * 0.0)
+        return hce, tau.detach(), k
+
+    def _run(self, logits, target, with_stats):
+        K = self.num_classes
+        target = self._label_map(logits, target)
+        with torch.autocast(logits.device.type, enabled=False):
+            rho = self._scalar(logits.device)
+            if logits.is_cuda and K <= 32:
+                from . import ops
+                z = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
+                rows = logits.shape[0] if self.per_sample else 1
+                res = ops.seg_hard(z, target, self.params, self.gamma, rho, self._weight(logits.device), self.ignore_index,
+                                   rows, self.include_background, with_stats)
+                self.last_terms = res[1]
+                return (res[0], res[2]) if with_stats else res[0]
+            z, t = logits.float(), target.long()
+            tv = self._terms_torch(z, t)[1]
+            hce, tau, k = self._hard_torch(z, t, rho)
+            self.last_terms = torch.stack([hce.detach().double(), tv.detach().double(), tau.double(), k.double()])
+            loss = self.ce * hce + self.tversky * tv
+            if not with_stats:
+                return loss
+            return loss, self.hard_stats(z.detach(), t)
+
+
+def focal_loss(num_classes: int, gamma: float = 2.0, class_weight=None, ignore_index: int = -100) -> HardExampleSegLoss:
+    """The multi-class focal loss: the weighted mean of (1 - p_t)^gamma (-log p_t)."""
+    return HardExampleSegLoss(num_classes, ce=1.0, tversky=0.0, class_weight=class_weight, ignore_index=ignore_index,
+                              gamma=gamma)
+
+
+def dice_focal_loss(num_classes: int, gamma: float = 2.0, focal: float = 1.0, dice: float = 1.0, smooth: float = 1.0,
+                    class_weight=None, ignore_index: int = -100, per_sample: bool = False,
+                    include_background: bool = True) -> HardExampleSegLoss:
+    """focal * focal loss + dice * mean over classes of (1 - Dice_c); smooth is Dice's, as in ce_dice_loss."""
+    return HardExampleSegLoss(num_classes, ce=focal, tversky=dice, alpha=0.5, beta=0.5, smooth=smooth / 2,
+                              class_weight=class_weight, ignore_index=ignore_index, per_sample=per_sample,
+                              include_background=include_background, gamma=gamma)
+
+
+def topk_ce_loss(num_classes: int, top_k: float = 0.1, class_weight=None, ignore_index: int = -100,
+                 schedule=None) -> HardExampleSegLoss:
+    """Cross-entropy averaged over the hardest top_k fraction of the batch's pixels (nnU-Net's TopKLoss, k = 10 %)."""
+    return HardExampleSegLoss(num_classes, ce=1.0, tversky=0.0, class_weight=class_weight, ignore_index=ignore_index,
+                              top_k=top_k, schedule=schedule)
+
+
+def dice_topk_loss(num_classes: int, top_k: float = 0.1, ce: float = 1.0, dice: float = 1.0, smooth: float = 1.0,
+                   class_weight=None, ignore_index: int = -100, per_sample: bool = False, include_background: bool = True,
+                   schedule=None) -> HardExampleSegLoss:
+    """ce * top-k CE + dice * mean over classes of (1 - Dice_c) (nnU-Net's DC_and_topk_loss); smooth is Dice's."""
+    return HardExampleSegLoss(num_classes, ce=ce, tversky=dice, alpha=0.5, beta=0.5, smooth=smooth / 2,
+                              class_weight=class_weight, ignore_index=ignore_index, per_sample=per_sample,
+                              include_background=include_background, top_k=top_k, schedule=schedule)

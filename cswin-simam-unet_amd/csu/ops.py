@@ -1676,6 +1676,119 @@ def seg_bd(logits: torch.Tensor, target: torch.Tensor, phi: torch.Tensor, w_bd: 
                           bool(include_background), bool(bd_background), bool(with_stats))
 
 
+def kth_largest(keys: torch.Tensor, rho: torch.Tensor) -> torch.Tensor:
+    """csu_kth_largest: the k-th largest of the fp32 device keys whose sign bit is clear (the others are skipped),
+    k = max(1, floor(rho n)) of the n such keys, rho a one-element fp32 device tensor.  Returns an fp64 (5,) device
+    tensor (tau, n_gt, n_eq, k, n); keys are compared by their bit patterns (csrc/kth_largest.hip).  No
+    synchronisation."""
+    require_device(keys, rho)
+    if keys.dtype != torch.float32 or keys.numel() < 1:
+        raise ValueError("kth_largest: a non-empty fp32 tensor of keys")
+    if rho.dtype != torch.float32 or rho.numel() != 1:
+        raise ValueError("kth_largest: rho is a one-element fp32 tensor")
+    keys = keys.contiguous()
+    cap = keys.numel()
+    out = torch.empty(5, dtype=torch.float64, device=keys.device)
+    nws = lib().csu_kth_largest_workspace(cap)
+    ws = torch.empty(nws // 8, dtype=torch.int64, device=keys.device)
+    _launch("kth_largest", lambda: lib().csu_kth_largest(cap, ptr(keys), ptr(rho), ptr(out), ptr(ws), nws,
+                                                         stream_ptr(keys.device)),
+            0, 4 * 4 * cap, prec="f32")
+    return out
+
+
+class _SegHardFn(torch.autograd.Function):
+    """_SegCEFn's loss with the hard-example CE term in the place of CE (csu_seg_hard_fwd / csu_seg_hard_bwd: the
+    same kernels with one more compile-time flag): per live pixel l = w[t] u^gamma L, u = sum_{k != t} p_k, L the
+    pixel's CE; without ``rho`` HCE = sum l / sum w[t], with it (a one-element fp32 device tensor the kernels read)
+    the mean over the k = max(1, floor(rho n)) largest l of the batch, ties at the threshold sharing the remaining
+    places.  The forward then also writes every l into an fp32 (B, HW) buffer that csu_kth_largest selects from
+    and the backward reads the selection from.  Also returns terms = fp64 (4,) (HCE, Tversky mean, tau, k),
+    non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, z, t, rho, gamma: float, params, cw, ignore_index: int, rows: int, include_background: bool,
+                with_stats: bool = False):
+        B, K = z.shape[0], z.shape[1]
+        z, sb, sk, sp, HW, pad_ok = _seg_ce_layout(z)
+        t = t.contiguous()
+        w_ce, w_tv, alpha, beta, smooth = (float(v) for v in params)
+        dev = z.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(4, dtype=torch.float64, device=dev)
+        stats = torch.empty(3, K, dtype=torch.float64, device=dev) if with_stats else None
+        coef = torch.empty(2 * rows * K + 3, dtype=torch.float32, device=dev)
+        keys = torch.empty(B * HW, dtype=torch.float32, device=dev) if rho is not None else None
+        nws = lib().csu_seg_hard_workspace(B, K, HW)
+        ws = torch.empty(nws // 8, dtype=torch.int64, device=dev)
+        lab = 1 if t.dtype == torch.int64 else 0
+        geom = (B, K, HW, rows, dtype_code(z), sb, sk, sp, int(pad_ok), lab, int(ignore_index), int(include_background))
+        nbytes = B * K * HW * z.element_size() + B * HW * t.element_size()
+        # with a selection: the keys written, four selection passes and one pass of selected sums over them (the
+        # last with the labels again when there are class weights)
+        sel_bytes = 0 if rho is None else B * HW * (4 + 4 * 4 + 4 + (t.element_size() if cw is not None else 0))
+        _launch("seg_hard", lambda: lib().csu_seg_hard_fwd(B, K, HW, rows, geom[4], ptr(z), sb, sk, sp, geom[8], lab, ptr(t),
+                                                           geom[10], ptr(cw), w_ce, w_tv, alpha, beta, smooth, geom[11],
+                                                           float(gamma), ptr(rho), ptr(keys), ptr(loss), ptr(terms),
+                                                           ptr(stats), ptr(coef), ptr(ws), nws, stream_ptr(dev)),
+                (12 * K + 60) * B * HW, nbytes + sel_bytes, prec="f32")
+        ctx.save_for_backward(z, t, coef, cw, keys)
+        ctx.seg = (geom, w_ce, w_tv, float(gamma), nbytes)
+        if with_stats:
+            ctx.mark_non_differentiable(terms, stats)
+            return loss, terms, stats
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        z, t, coef, cw, keys = ctx.saved_tensors
+        (B, K, HW, rows, dt, sb, sk, sp, pad_ok, lab, ignore, bg), w_ce, w_tv, gamma, nbytes = ctx.seg
+        g = g.float().contiguous()
+        es = z.element_size()      # dz: the logits' strides and offset within 16 B, as _SegCEFn.backward
+        off = (z.data_ptr() % 16) // es
+        need = (B - 1) * sb + (HW - 1) * sp + max((K - 1) * sk + 1, _seg_ce_bucket(K) if pad_ok else 0)
+        dz = torch.empty(off + need, dtype=z.dtype, device=z.device).as_strided(z.shape, z.stride(), off)
+        _launch("seg_hard_bwd", lambda: lib().csu_seg_hard_bwd(B, K, HW, rows, dt, ptr(z), sb, sk, sp, pad_ok, lab, ptr(t),
+                                                               ignore, ptr(cw), ptr(g), ptr(coef), w_ce, w_tv, bg, gamma,
+                                                               ptr(keys), ptr(dz), stream_ptr(z.device)),
+                (14 * K + 80) * B * HW, nbytes + B * K * HW * es + (0 if keys is None else 4 * B * HW), prec="f32")
+        return (dz,) + (None,) * 9
+
+
+def seg_hard(logits: torch.Tensor, target: torch.Tensor, params, gamma: float = 0.0, rho: Optional[torch.Tensor] = None,
+             class_weight: Optional[torch.Tensor] = None, ignore_index: int = -100, rows: int = 1,
+             include_background: bool = True, with_stats: bool = False):
+    """seg_ce's loss with the hard-example CE term (see _SegHardFn): gamma >= 0 is the focal exponent, rho a
+    one-element fp32 device tensor with the top-k fraction, or None for no selection.  Returns (loss, terms) or,
+    with_stats, (loss, terms, fp64 (3, K) hard sums); terms = fp64 (4,) (HCE, Tversky mean, tau, k)."""
+    require_device(logits, target, class_weight, rho)
+    if logits.dim() < 2 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("seg_hard: fp32 or bf16 logits (B, K, *spatial)")
+    B, K = logits.shape[0], logits.shape[1]
+    if not 2 <= K <= SEG_CE_MAX_CLASSES:
+        raise ValueError(f"seg_hard: 2 <= K <= {SEG_CE_MAX_CLASSES} classes (got {K})")
+    if target.dtype not in (torch.int64, torch.uint8) or tuple(target.shape) != (B,) + tuple(logits.shape[2:]):
+        raise ValueError("seg_hard: int64 or uint8 target of the logits' shape without the class dim")
+    if logits.numel() < 1:
+        raise ValueError("seg_hard: empty logits")
+    if not 0.0 <= float(gamma) < float("inf"):
+        raise ValueError("seg_hard: gamma must be a finite number >= 0")
+    if rho is not None and (rho.dtype != torch.float32 or rho.numel() != 1):
+        raise ValueError("seg_hard: rho is a one-element fp32 tensor, or None")
+    rows = int(rows)
+    if rows not in (1, B):
+        raise ValueError("seg_hard: rows must be 1 or the batch size")
+    if len(params) != 5:
+        raise ValueError("seg_hard: params = (w_ce, w_tversky, alpha, beta, smooth)")
+    if class_weight is not None:
+        if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (K,):
+            raise ValueError("seg_hard: class_weight is an fp32 (K,) tensor")
+        class_weight = class_weight.contiguous()
+    return _SegHardFn.apply(logits, target, None if rho is None else rho.detach(), float(gamma), tuple(params), class_weight,
+                            int(ignore_index), rows, bool(include_background), bool(with_stats))
+
+
 SIGNED_DISTANCE_MAX_DIM = 16383
 
 

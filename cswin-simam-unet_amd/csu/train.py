@@ -426,7 +426,8 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
     Schedules: a criterion with an ``on_epoch(epoch)`` method (csu.losses.BoundarySegLoss) gets that call at the
     start of every epoch, before the first step; one with a ``boundary_weight`` adds the history key
     ``boundary_weight``, the weight each epoch trained with.  The weight is a device scalar the captured step
-    reads, so the change needs no re-capture."""
+    reads, so the change needs no re-capture.  Likewise a criterion whose ``top_k`` is not None
+    (csu.losses.HardExampleSegLoss) adds the history key ``top_k``, the fraction each epoch trained with."""
     history = {"train_loss": [], "train_dice": [], "train_iou": [], "test_loss": [], "test_dice": [], "test_iou": [],
                "learning_rates": []}
     clips = _clips(optimizer)
@@ -440,6 +441,8 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
         history["ema_test_loss"], history["ema_test_dice"], history["ema_test_iou"] = [], [], []
     if hasattr(criterion, "boundary_weight"):
         history["boundary_weight"] = []
+    if getattr(criterion, "top_k", None) is not None:
+        history["top_k"] = []
     rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
     start = 0
     if resume_from is not None:
@@ -462,6 +465,8 @@ def train_model(model, train_loader, test_loader, criterion, optimizer, schedule
             criterion.on_epoch(epoch)
         if hasattr(criterion, "boundary_weight"):
             history["boundary_weight"].append(criterion.boundary_weight)
+        if "top_k" in history:
+            history["top_k"].append(criterion.top_k)
         model.train()
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):

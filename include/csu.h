@@ -892,6 +892,55 @@ int csu_seg_bd_bwd(int B, int K, long HW, int rows, int dtype, const void* z, lo
                    const float* w_bd, int bd_background, void* dz, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The k-th largest of cap fp32 keys, k a fraction of the live ones (csrc/kth_largest.hip): the threshold of
+ * the top-k cross-entropy below; the reference has no counterpart.
+ *   keys: cap floats on the device; a key with the sign bit set is skipped.  The others are compared by their
+ *         bit patterns, which order +0, denormals, normals and +inf as their values do (a NaN sorts above +inf).
+ *   rho:  one float on the device.  n = the keys not skipped, k = max(1, floor((double)rho[0] n)), at most n.
+ *   out:  5 doubles on the device: tau = the k-th largest key (exactly the float), n_gt = #{key > tau},
+ *         n_eq = #{key = tau}, k, n.  n = 0: all zero.
+ * A 4 x 8-bit radix select with integer histograms: exact, the same for any order of the keys, nothing returns
+ * to the host, and no loop bound is read from device memory.  Workspace csu_kth_largest_workspace(cap) bytes,
+ * 8-byte aligned (0: cap < 1).
+ * CSU_E_ARG: cap < 1 or > 2^40, a null or misaligned pointer.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_kth_largest_workspace(long cap);
+int csu_kth_largest(long cap, const float* keys, const float* rho, double* out, void* workspace, size_t ws_bytes,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The multi-class loss with a hard-example CE term: focal weighting (Lin et al. 2017) and / or a top-k
+ * selection over the batch (nnU-Net's TopKLoss); csrc/seg_ce.hip, the kernels above with one more
+ * compile-time flag.  The reference has no counterpart.  Every argument of csu_seg_ce_* keeps its meaning; added:
+ *   gamma: >= 0, finite.   rho: one float on the device, or NULL for no selection.
+ *   keys:  B HW floats, written by fwd and read by bwd; NULL exactly when rho is.
+ * For a live pixel (label in [0, K), not ignore_index), p = softmax(z), q = p_t:
+ *   u = sum_{k != t} p_k,  L = logsumexp(z) - z_t,  l = w[t] u^gamma L   (u^gamma = 1 at gamma = 0; l >= +0)
+ *   no rho: HCE = sum l / sum w[t]                                                    (0 when sum w[t] = 0)
+ *   rho:    (tau, n_gt, n_eq, k, n) = csu_kth_largest of the l (keys[pix] = l, a dead pixel: -1), f = (k - n_gt) / n_eq,
+ *           m = 1 (l > tau), f (l = tau), 0 (l < tau),  HCE = sum m l / sum m w[t]   (0 when the denominator W is 0)
+ *   loss[0] = w_ce HCE + w_tversky mean_r mean_{c in C} (1 - TI_rc);  terms = fp64 {HCE, the Tversky mean, tau, k}
+ *             (no rho: tau = 0, k = the live pixels)
+ *   dz_k = dloss[0] (w_ce m w[t] (p_k - [k = t]) (u^gamma + gamma q u^(gamma - 1) L) / W - the Tversky part of csu_seg_ce_bwd);
+ *          the second summand is 0 at gamma = 0, u = 0 or L = 0.  m is taken from keys and tau, never from an l
+ *          formed again.
+ * coef: 2 rows K + 3 floats (A, C per (row, class), then 1 / W, tau, f).  Workspace csu_seg_hard_workspace(B, K, HW)
+ * bytes (a multiple of 8), 8-byte aligned: csu_kth_largest's, 6 doubles, and (5 + 5 K) floats per (image, chunk) item.
+ * Deterministic: fixed-order sums and integer atomics only.
+ * CSU_E_ARG: as csu_seg_ce_*, gamma negative or not finite, rho without keys or keys without rho, a null terms.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_seg_hard_workspace(int B, int K, long HW);
+int csu_seg_hard_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix, int pad_ok,
+                     int label_dtype, const void* t, long ignore_index, const float* class_weight, float w_ce,
+                     float w_tversky, float alpha, float beta, float smooth, int include_background, float gamma,
+                     const float* rho, float* keys, float* loss, double* terms, double* stats, float* coef,
+                     void* workspace, size_t ws_bytes, void* stream);
+int csu_seg_hard_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix, int pad_ok,
+                     int label_dtype, const void* t, long ignore_index, const float* class_weight, const float* dloss,
+                     const float* coef, float w_ce, float w_tversky, int include_background, float gamma,
+                     const float* keys, void* dz, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mask-aligned batch augmentation (AugmentationTransform cswin:20-87 + the dataset's /255 and
  * HWC -> CHW, cswin:166-173), square S x S images: img uint8 (B, S, S, 3), mask uint8 (B, S, S),
  * params int32 (B, 7) on the device = {hflip, vflip, clockwise quarter turns 0..3, crop top,
