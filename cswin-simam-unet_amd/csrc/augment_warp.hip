@@ -7,9 +7,10 @@
 //                         affine (composed in fp64, rounded once) of table row b
 //   augment_ctrl_kernel   the control displacements, 4 per Philox call
 //   augment_sum_kernel    exact integer byte sum per image (16-byte loads, v_sad_u8, one 64-bit atomic per block)
-//   augment_warp_kernel   the hot one: a 64 x 4 output tile per 256-thread block (each wave stores 256
+//   warp_kernel<POOL>     the hot one: a 64 x 4 output tile per 256-thread block (each wave stores 256
 //                         contiguous bytes per plane), the tile's control points staged in LDS, a gather of the
-//                         4 bilinear taps from the uint8 source, intensity steps in registers, one pass, no atomics
+//                         4 bilinear taps from the uint8 source, intensity steps in registers, one pass, no atomics;
+//                         the source is a batch of the output's size, or per slot an image of a patch pool
 #include "common.hpp"
 #include "rng.hpp"
 
@@ -20,20 +21,11 @@ constexpr int NT = 256;
 constexpr int P = CSU_AUGMENT_P;
 constexpr int TX = 64, TY = 4;                 // output tile of the warp kernel
 constexpr int MIN_SPACING = 4;
+constexpr int ORIGIN_MAX = 1 << 24;            // a patch origin beyond it is clamped (floats stay exact)
 constexpr int CX = TX / MIN_SPACING + 4;       // control points a tile can need at the smallest spacing
 constexpr int CY = TY / MIN_SPACING + 4;
 enum { T_HFLIP, T_VFLIP, T_ROT90, T_ANGLE, T_SCALE, T_TX, T_TY, T_CONTRAST, T_BRIGHT, T_GAMMA, T_SIGMA, T_ELASTIC, T_A };
 
-struct Snap { uint32_t k0, k1, c2, c3; };
-__device__ __forceinline__ Snap load_snap(const uint64_t* rng) {
-    const uint64_t seed = rng[0], ctr = rng[1];
-    return {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32)};
-}
-// the Philox call `e` of image b under `site`
-__device__ __forceinline__ uint4 draw4(const Snap& s, uint32_t e, int b, uint32_t site) {
-    return philox4x32_7(e, ((uint32_t)b << 12) ^ site, s.c2, s.c3, s.k0, s.k1);
-}
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.f / 16777216.f); }   // [0, 1), exact
 __device__ __forceinline__ float in_range(float u, float lo, float hi) { return fminf(fmaxf(lo + u * (hi - lo), lo), hi); }
 
 __global__ __launch_bounds__(NT) void augment_draw_kernel(csu_augment_config cfg, int B, int H, int W,
@@ -167,13 +159,23 @@ __device__ __forceinline__ void bspline(float f, float* w) {
     w[3] = f3 * (1.f / 6.f);
 }
 
-// grid (tiles in x, tiles in y, images): the tile comes from the block index with no division; the pointers are
-// restrict kernel arguments, so the block-uniform table row is read with scalar loads
-__global__ __launch_bounds__(NT) void augment_warp_kernel(WarpArgs a, const uint8_t* __restrict__ img,
-                                                          const uint8_t* __restrict__ mask, const float* __restrict__ table,
-                                                          const float* __restrict__ ctrl, const float* __restrict__ means,
-                                                          const uint64_t* __restrict__ rng, float* __restrict__ oimg,
-                                                          void* __restrict__ omask) {
+// Both warp kernels.  POOL = false: slot b reads image b of an (B, H, W) batch, the output's size
+// (csu_augment_warp; meta, record and N are unused).  POOL = true: slot b reads image record[b][0] of a patch pool
+// (csu_patch_warp): its own H_n x W_n, pixel offset and mean from meta / means, the patch's integer origin (ox, oy)
+// from the record.  The source position is evaluated in the output's frame and the origin is added to the integer
+// tap coordinates only, so its precision does not depend on where in a large image the patch lies; with origin 0
+// and equal sizes the arithmetic is the batch kernel's operation for operation.  The kernel itself is the
+// template: as an inlined device function the same body loses the kernel arguments' noalias and schedules
+// differently (3 VGPRs more); this way the POOL = false instantiation is instruction for instruction what it was.
+// grid (tiles in x, tiles in y, slots): the tile comes from the block index with no division; the pointers are
+// restrict kernel arguments, so the block-uniform table, record and meta rows are read with scalar loads
+template <bool POOL>
+__global__ __launch_bounds__(NT) void warp_kernel(WarpArgs a, const uint8_t* __restrict__ img,
+                                                  const uint8_t* __restrict__ mask, const float* __restrict__ table,
+                                                  const float* __restrict__ ctrl, const float* __restrict__ means,
+                                                  const uint64_t* __restrict__ rng, float* __restrict__ oimg,
+                                                  void* __restrict__ omask, const long long* __restrict__ meta,
+                                                  const int* __restrict__ record, int N) {
     __shared__ float cs[2][CY][CX];
     const int H = a.H, W = a.W, sp = a.spacing;
     const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x / TX;
@@ -195,6 +197,17 @@ __global__ __launch_bounds__(NT) void augment_warp_kernel(WarpArgs a, const uint
             __syncthreads();
         }
         if (x >= W || y >= H) continue;     // no barrier below
+        // the source of this slot: SH x SW pixels from pixel `pbase` on, the output's (0, 0) at (ox, oy) in it
+        int SH = H, SW = W, ox = 0, oy = 0, mi = b;
+        long pbase = 0;
+        if constexpr (POOL) {
+            const int* rec = record + (long)b * CSU_PATCH_RECORD;
+            mi = min(max(rec[0], 0), N - 1);
+            const long long* m = meta + (long)mi * 4;
+            pbase = (long)m[0]; SH = (int)m[1]; SW = (int)m[2];
+            oy = min(max(rec[4], -ORIGIN_MAX), ORIGIN_MAX);
+            ox = min(max(rec[5], -ORIGIN_MAX), ORIGIN_MAX);
+        }
         float px = (float)x, py = (float)y;
         if (elastic) {
             const int ix = x / sp, iy = y / sp;
@@ -219,14 +232,17 @@ __global__ __launch_bounds__(NT) void augment_warp_kernel(WarpArgs a, const uint
         float sy = fmaf(row[T_A + 3], px, fmaf(row[T_A + 4], py, row[T_A + 5]));
         // replicate: the coordinate is clamped to the image; constant: to a band in which every tap is
         // still outside (keeps the integer conversions in range for any table, NaN included)
-        sx = replicate ? fminf(fmaxf(sx, 0.f), (float)(W - 1)) : fminf(fmaxf(sx, -2.f), (float)(W + 1));
-        sy = replicate ? fminf(fmaxf(sy, 0.f), (float)(H - 1)) : fminf(fmaxf(sy, -2.f), (float)(H + 1));
+        // (in the output's frame: the bounds are the source's less the origin, exact floats below 2^24)
+        sx = replicate ? fminf(fmaxf(sx, (float)(0 - ox)), (float)(SW - 1 - ox))
+                       : fminf(fmaxf(sx, (float)(-2 - ox)), (float)(SW + 1 - ox));
+        sy = replicate ? fminf(fmaxf(sy, (float)(0 - oy)), (float)(SH - 1 - oy))
+                       : fminf(fmaxf(sy, (float)(-2 - oy)), (float)(SH + 1 - oy));
         const float flx = floorf(sx), fly = floorf(sy);
         const float fx = sx - flx, fy = sy - fly;
-        const int xi[2] = {(int)flx, (int)flx + 1}, yi[2] = {(int)fly, (int)fly + 1};
+        const int xi[2] = {(int)flx + ox, (int)flx + ox + 1}, yi[2] = {(int)fly + oy, (int)fly + oy + 1};
         const float wx2[2] = {1.f - fx, fx}, wy2[2] = {1.f - fy, fy};
         const bool bilinear_mask = a.mask_mode == CSU_AUG_MASK_BILINEAR;
-        const long ibase = (long)b * H * W;
+        const long ibase = POOL ? pbase : (long)b * H * W;
         // Every load is unconditional, from a clamped (always legal) address, and all are issued before the first
         // use: a load written under `inside ? load : fill` compiles to a branch and a full wait per tap.
         long pix[4];
@@ -236,13 +252,13 @@ __global__ __launch_bounds__(NT) void augment_warp_kernel(WarpArgs a, const uint
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                in[2 * i + j] = replicate || ((unsigned)yi[i] < (unsigned)H && (unsigned)xi[j] < (unsigned)W);
-                pix[2 * i + j] = ibase + (long)min(max(yi[i], 0), H - 1) * W + min(max(xi[j], 0), W - 1);
+                in[2 * i + j] = replicate || ((unsigned)yi[i] < (unsigned)SH && (unsigned)xi[j] < (unsigned)SW);
+                pix[2 * i + j] = ibase + (long)min(max(yi[i], 0), SH - 1) * SW + min(max(xi[j], 0), SW - 1);
                 w[2 * i + j] = wy2[i] * wx2[j];
             }
-        const int nxi = (int)floorf(sx + 0.5f), nyi = (int)floorf(sy + 0.5f);
-        const bool nin = replicate || ((unsigned)nyi < (unsigned)H && (unsigned)nxi < (unsigned)W);
-        const long npix = ibase + (long)min(max(nyi, 0), H - 1) * W + min(max(nxi, 0), W - 1);
+        const int nxi = (int)floorf(sx + 0.5f) + ox, nyi = (int)floorf(sy + 0.5f) + oy;
+        const bool nin = replicate || ((unsigned)nyi < (unsigned)SH && (unsigned)nxi < (unsigned)SW);
+        const long npix = ibase + (long)min(max(nyi, 0), SH - 1) * SW + min(max(nxi, 0), SW - 1);
         uint8_t tap[4][3], mtap[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -258,7 +274,7 @@ __global__ __launch_bounds__(NT) void augment_warp_kernel(WarpArgs a, const uint
             acc[3] += w[k] * (in[k] ? (float)mtap[k] : 0.f);
         }
         const float contrast = row[T_CONTRAST], bright = row[T_BRIGHT], gamma = row[T_GAMMA];
-        const float sigma = rng ? row[T_SIGMA] : 0.f, mean = means[b];
+        const float sigma = rng ? row[T_SIGMA] : 0.f, mean = means[mi];
         float n[3] = {0.f, 0.f, 0.f};
         if (sigma > 0.f) {
             const uint4 v = draw4(load_snap(rng), (uint32_t)(y * W + x), b, a.site);
@@ -355,7 +371,31 @@ extern "C" int csu_augment_warp(int B, int H, int W, const void* img, const void
     a.site = noise_site;
     a.spacing = ctrl ? spacing : 0; a.border = border; a.mask_mode = mask_mode; a.pad_label = pad_label;
     a.fill = image_fill * 255.f;
-    augment_warp_kernel<<<dim3((unsigned)ntx, (unsigned)nty, (unsigned)(B > 65535 ? 65535 : B)), NT, 0, as_stream(stream)>>>(
-        a, (const uint8_t*)img, (const uint8_t*)mask, table, ctrl, mean, rng, out_img, out_mask);
+    warp_kernel<false><<<dim3((unsigned)ntx, (unsigned)nty, (unsigned)(B > 65535 ? 65535 : B)), NT, 0, as_stream(stream)>>>(
+        a, (const uint8_t*)img, (const uint8_t*)mask, table, ctrl, mean, rng, out_img, out_mask, nullptr, nullptr, 0);
     return check_launch("augment_warp");
+}
+
+extern "C" int csu_patch_warp(int B, int Ph, int Pw, int N, const void* pixels, const void* labels, const int64_t* meta,
+                              const float* mean, const int32_t* record, const float* table, const float* ctrl, int spacing,
+                              const uint64_t* rng, unsigned noise_site, int border, float image_fill, int pad_label,
+                              int mask_mode, float* out_img, void* out_mask, void* stream) {
+    if (B < 1 || B > (1 << 20) || Ph < 1 || Pw < 1 || (long)Ph * Pw >= (1L << 31) || N < 1 || N > (1 << 20) || !pixels ||
+        !labels || !meta || !mean || !record || !table || !out_img || !out_mask || noise_site >= 4096u)
+        return fail(CSU_E_ARG, "patch_warp: bad args");
+    if (ctrl && spacing < MIN_SPACING) return fail(CSU_E_ARG, "patch_warp: control-grid spacing below 4");
+    if ((border != CSU_AUG_CONSTANT && border != CSU_AUG_REPLICATE) || mask_mode < CSU_AUG_MASK_BILINEAR ||
+        mask_mode > CSU_AUG_MASK_LABELS || !(image_fill >= 0.f && image_fill <= 1.f))
+        return fail(CSU_E_ARG, "patch_warp: bad border, mask mode or image_fill");
+    const int ntx = (Pw + TX - 1) / TX, nty = (Ph + TY - 1) / TY;
+    if (nty > 65535) return fail(CSU_E_ARG, "patch_warp: patch too tall");
+    WarpArgs a;
+    a.B = B; a.H = Ph; a.W = Pw;
+    a.site = noise_site;
+    a.spacing = ctrl ? spacing : 0; a.border = border; a.mask_mode = mask_mode; a.pad_label = pad_label;
+    a.fill = image_fill * 255.f;
+    warp_kernel<true><<<dim3((unsigned)ntx, (unsigned)nty, (unsigned)(B > 65535 ? 65535 : B)), NT, 0, as_stream(stream)>>>(
+        a, (const uint8_t*)pixels, (const uint8_t*)labels, table, ctrl, mean, rng, out_img, out_mask, (const long long*)meta,
+        record, N);
+    return check_launch("patch_warp");
 }

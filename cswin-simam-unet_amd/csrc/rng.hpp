@@ -37,6 +37,18 @@ __device__ __forceinline__ uint4 philox4x32_7(uint32_t c0, uint32_t c1, uint32_t
     return make_uint4(c0, c1, c2, c3);
 }
 
+// The per-image draws of the augmentation and patch kernels (augment_warp.hip, patch.hip): the [seed, counter]
+// snapshot, and the Philox call `e` of image / slot b under `site`
+struct Snap { uint32_t k0, k1, c2, c3; };
+__device__ __forceinline__ Snap load_snap(const uint64_t* rng) {
+    const uint64_t seed = rng[0], ctr = rng[1];
+    return {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32)};
+}
+__device__ __forceinline__ uint4 draw4(const Snap& s, uint32_t e, int b, uint32_t site) {
+    return philox4x32_7(e, ((uint32_t)b << 12) ^ site, s.c2, s.c3, s.k0, s.k1);
+}
+__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.f / 16777216.f); }   // [0, 1), exact
+
 // The per-step RNG snapshot a dropout site reads: [seed, counter] (two 64-bit words in HBM).
 struct DropoutRng {
     uint32_t k0, k1, c2, c3;   // key = seed, counter words 2/3 = step counter

@@ -23,6 +23,7 @@ from .boundary import reference_signed_distance_map, signed_distance_map
 from .components import (PostProcess, connected_components, postprocess_labels, reference_connected_components,
                          reference_postprocess_labels)
 from .augment import SpatialAugment, reference_augment
+from .patches import PatchLoader, PatchPool, PatchSampler, reference_patch_sample
 from . import rng
 from .rng import manual_seed
 
@@ -37,4 +38,4 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "reference_connected_components", "reference_postprocess_labels", "SpatialAugment", "reference_augment",
            "BoundarySegLoss", "boundary_loss", "ce_dice_boundary_loss", "linear_ramp", "signed_distance_map",
            "reference_signed_distance_map", "HardExampleSegLoss", "focal_loss", "dice_focal_loss", "topk_ce_loss",
-           "dice_topk_loss"]
+           "dice_topk_loss", "PatchPool", "PatchSampler", "PatchLoader", "reference_patch_sample"]

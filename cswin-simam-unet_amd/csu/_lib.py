@@ -223,6 +223,13 @@ _SIGS = {
                                                                              ctypes.c_uint, ctypes.c_int, c_float,
                                                                              ctypes.c_int, ctypes.c_int, c_void_p, c_void_p,
                                                                              c_void_p]),
+    "csu_patch_index": (ctypes.c_int, [ctypes.c_int] * 3 + [c_void_p] * 4),
+    "csu_patch_draw": (ctypes.c_int, [c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_uint] + [ctypes.c_int] * 4
+                       + [c_float, c_void_p, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
+    "csu_patch_locate": (ctypes.c_int, [c_void_p] * 3 + [ctypes.c_int] * 3 + [c_void_p] * 5),
+    "csu_patch_warp": (ctypes.c_int, [ctypes.c_int] * 4 + [c_void_p] * 7 + [ctypes.c_int, c_void_p, ctypes.c_uint,
+                                                                           ctypes.c_int, c_float, ctypes.c_int, ctypes.c_int,
+                                                                           c_void_p, c_void_p, c_void_p]),
     "csu_tile_gather": (ctypes.c_int, [ctypes.c_int] * 5 + [c_void_p] * 4),
     "csu_tile_blend": (ctypes.c_int, [ctypes.c_int] * 7 + [c_void_p] + [ctypes.c_long] * 3 + [ctypes.c_int]
                        + [c_void_p] * 3 + [ctypes.c_int] * 4 + [c_void_p]),

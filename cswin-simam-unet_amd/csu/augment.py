@@ -24,7 +24,7 @@ TABLE_P = 20
 (T_HFLIP, T_VFLIP, T_ROT90, T_ANGLE, T_SCALE, T_TX, T_TY, T_CONTRAST, T_BRIGHTNESS, T_GAMMA, T_SIGMA,
  T_ELASTIC, T_A) = range(13)
 
-__all__ = ["SpatialAugment", "reference_augment", "reference_source_coords", "compose_affine", "identity_table",
+__all__ = ["SpatialAugment", "reference_augment", "reference_source_coords", "reference_sample_at", "compose_affine", "identity_table",
            "make_table", "control_grid", "TABLE_P"]
 
 
@@ -105,6 +105,13 @@ def reference_source_coords(table: torch.Tensor, ctrl: Optional[torch.Tensor], s
     return a[:, 0] * px + a[:, 1] * py + a[:, 2], a[:, 3] * px + a[:, 4] * py + a[:, 5]
 
 
+def _check_modes(who, border, mask_mode, out):
+    if border not in ("constant", "replicate") or (mask_mode, out) not in (("bilinear", "binary"), ("nearest", "binary"),
+                                                                          ("nearest", "labels")):
+        raise ValueError(f"{who}: border constant / replicate; mask_mode bilinear / nearest; out binary, or "
+                         "labels with nearest")
+
+
 def reference_augment(images: torch.Tensor, masks: torch.Tensor, table: torch.Tensor, ctrl: Optional[torch.Tensor] = None,
                       *, spacing: int = 0, border: str = "constant", image_fill: float = 0.0, pad_label: int = 0,
                       mask_mode: str = "bilinear", out: str = "binary", noise: Optional[torch.Tensor] = None):
@@ -112,37 +119,48 @@ def reference_augment(images: torch.Tensor, masks: torch.Tensor, table: torch.Te
     (B, H, W, 3) and masks (B, H, W) -> fp32 (B, 3, H, W) and fp32 (B, 1, H, W) or int64 (B, H, W) labels.
     ``noise``: standard normals (B, 3, H, W) scaled by the rows' sigma, or None for no noise (the kernel's
     own normals come from its Philox stream)."""
-    if border not in ("constant", "replicate") or (mask_mode, out) not in (("bilinear", "binary"), ("nearest", "binary"),
-                                                                          ("nearest", "labels")):
-        raise ValueError("reference_augment: border constant / replicate; mask_mode bilinear / nearest; out binary, or "
-                         "labels with nearest")
+    _check_modes("reference_augment", border, mask_mode, out)
     B, H, W = images.shape[:3]
+    sx, sy = reference_source_coords(table, ctrl, spacing, H, W)
+    return reference_sample_at(images, masks, table, sx, sy, border=border, image_fill=image_fill, pad_label=pad_label,
+                               mask_mode=mask_mode, out=out, noise=noise)
+
+
+def reference_sample_at(images: torch.Tensor, masks: torch.Tensor, table: torch.Tensor, sx: torch.Tensor, sy: torch.Tensor,
+                        *, border: str = "constant", image_fill: float = 0.0, pad_label: int = 0,
+                        mask_mode: str = "bilinear", out: str = "binary", noise: Optional[torch.Tensor] = None,
+                        mean: Optional[torch.Tensor] = None):
+    """reference_augment from given source positions on: fp64 (B, h, w) ``sx``, ``sy`` in the pixel coordinates of
+    the uint8 images (B, H, W, 3) / masks (B, H, W) -> the border rule, the bilinear / nearest samples and the
+    table's intensity chain, as fp32 (B, 3, h, w) and the mask.  The output h x w need not be H x W (a patch of a
+    larger image: csu.patches).  ``mean``: fp64 (B,) in [0, 1] for the contrast step (default: each image's own)."""
+    _check_modes("reference_sample_at", border, mask_mode, out)
+    B, H, W = images.shape[:3]
+    h, w_ = sx.shape[1:]
     dev = images.device
     t = table.double()
-    sx, sy = reference_source_coords(table, ctrl, spacing, H, W)
     rep = border == "replicate"
     sx = sx.clamp(0, W - 1) if rep else sx.clamp(-2, W + 1)      # constant: a band where every tap is still outside
     sy = sy.clamp(0, H - 1) if rep else sy.clamp(-2, H + 1)
     x0, y0 = torch.floor(sx), torch.floor(sy)
     fx, fy = sx - x0, sy - y0
     x0, y0 = x0.long(), y0.long()
-    bi = torch.arange(B, device=dev)[:, None, None].expand(B, H, W)
-    img, msk = images.double(), masks.double()
+    bi = torch.arange(B, device=dev)[:, None, None].expand(B, h, w_)
     fill = float(torch.tensor(image_fill, dtype=torch.float32)) * 255.0
-    acc, macc = torch.zeros(B, H, W, 3, dtype=torch.float64, device=dev), torch.zeros(B, H, W, dtype=torch.float64, device=dev)
+    acc, macc = torch.zeros(B, h, w_, 3, dtype=torch.float64, device=dev), torch.zeros(B, h, w_, dtype=torch.float64, device=dev)
     for i, wy in ((0, 1.0 - fy), (1, fy)):
         for j, wx in ((0, 1.0 - fx), (1, fx)):
             yy, xx = y0 + i, x0 + j
             inside = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W) if not rep else torch.ones_like(yy, dtype=torch.bool)
             yc, xc = yy.clamp(0, H - 1), xx.clamp(0, W - 1)
             w = wy * wx
-            acc += w[..., None] * torch.where(inside[..., None], img[bi, yc, xc], torch.full_like(acc, fill))
-            macc += w * torch.where(inside, msk[bi, yc, xc], torch.zeros_like(macc))
+            acc += w[..., None] * torch.where(inside[..., None], images[bi, yc, xc].double(), torch.full_like(acc, fill))
+            macc += w * torch.where(inside, masks[bi, yc, xc].double(), torch.zeros_like(macc))
     v = acc.permute(0, 3, 1, 2) / 255.0
 
     def col(i):
         return t[:, i, None, None, None]
-    mean = img.mean(dim=(1, 2, 3))[:, None, None, None] / 255.0
+    mean = (images.double().mean(dim=(1, 2, 3)) / 255.0 if mean is None else mean.double())[:, None, None, None]
     contrast, bright, gamma, sigma = col(T_CONTRAST), col(T_BRIGHTNESS), col(T_GAMMA), col(T_SIGMA)
     v = torch.where(contrast != 1, (v - mean) * contrast + mean, v)     # a step at its identity value is skipped
     v = torch.where(bright != 1, v * bright, v)

@@ -183,7 +183,11 @@ class SegmentationDataset(torch.utils.data.Dataset):
 
     ``raw=True`` (either mode): ``load()``'s resized uint8 (H, W, 3) image and uint8 (H, W) mask / label map
     as tensors, not augmented on the host, for ``DeviceAugmentLoader(loader, device, augment=SpatialAugment(...))``
-    (csu.augment), which samples label maps nearest-neighbour.  Label values above 255 raise."""
+    (csu.augment), which samples label maps nearest-neighbour.  Label values above 255 raise.
+
+    ``image_size=None`` (needs ``raw=True``): nothing is resized, every case comes at its file's own size (a mask
+    of another size than its image is resized to the image's), for ``csu.patches.PatchPool.from_dataset``; the
+    cases then differ in size and cannot be batched by a DataLoader."""
 
     def __init__(self, image_dir, mask_dir, image_size=(224, 224), augment=False, device_augment=False, label_mode=False,
                  raw=False):
@@ -192,9 +196,12 @@ class SegmentationDataset(torch.utils.data.Dataset):
         if label_mode and device_augment:
             raise ValueError("SegmentationDataset: label_mode=True cannot be combined with device_augment=True "
                              "(the device augmentation interpolates the mask bilinearly)")
+        if image_size is None and not raw:
+            raise ValueError("SegmentationDataset: image_size=None (cases at their own size) needs raw=True")
         self.label_mode = bool(label_mode)
         self.raw = bool(raw)
-        self.image_dir, self.mask_dir, self.image_size = image_dir, mask_dir, tuple(image_size)
+        self.image_dir, self.mask_dir = image_dir, mask_dir
+        self.image_size = None if image_size is None else tuple(image_size)
         self.augment, self.device_augment = augment, device_augment
         self.transform = AugmentationTransform(flip_prob=0.5, rotate_prob=0.25, crop_scale=(0.75, 1.0)) if augment else None
         self.image_paths = sorted(glob.glob(os.path.join(image_dir, "*.jpg")))
@@ -207,7 +214,8 @@ class SegmentationDataset(torch.utils.data.Dataset):
         return len(self.image_paths)
 
     def load(self, idx):
-        """(image uint8 (H, W, 3) RGB, mask uint8 (H, W)) resized to image_size, not augmented."""
+        """(image uint8 (H, W, 3) RGB, mask uint8 (H, W)) resized to image_size (None: the image's own), not
+        augmented."""
         import os
         from PIL import Image
         path = self.image_paths[idx]
@@ -220,12 +228,16 @@ class SegmentationDataset(torch.utils.data.Dataset):
                 mask = np.asarray(m if m.mode in ("P", "L", "I", "I;16") else m.convert("L"))     # raw indices
             except (FileNotFoundError, OSError):
                 mask = np.zeros(image.shape[:2], dtype=np.uint8)
+            if self.image_size is None:
+                return image.copy(), mask.copy() if mask.shape == image.shape[:2] else resize_nearest(mask, *image.shape[:2])
             w, h = self.image_size
             return resize_bilinear_u8(image, h, w), resize_nearest(mask, h, w)
         try:
             mask = np.asarray(Image.open(mpath).convert("L"))
         except (FileNotFoundError, OSError):
             mask = np.zeros(image.shape[:2], dtype=np.uint8)
+        if self.image_size is None:
+            return image.copy(), mask.copy() if mask.shape == image.shape[:2] else resize_bilinear_u8(mask, *image.shape[:2])
         w, h = self.image_size            # cv2.resize(image, dsize=(w, h)) (cswin:160-161)
         return resize_bilinear_u8(image, h, w), resize_bilinear_u8(mask, h, w)
 

@@ -1942,6 +1942,116 @@ def augment_warp(images: torch.Tensor, masks: torch.Tensor, table: torch.Tensor,
     return oimg, om
 
 
+PATCH_RECORD = 16                                # CSU_PATCH_RECORD: int32 per row of the draw's record (csu.patches.R_*)
+
+
+def patch_index(labels: torch.Tensor, meta: torch.Tensor, num_classes: int, max_h: int, entries: int) -> torch.Tensor:
+    """csu_patch_index: the int32 row index (`entries` values, laid out by meta[:, 3]) of a pool's packed uint8
+    `labels` and int64 (N, 4) `meta` (include/csu.h, "Patch pool")."""
+    require_device(labels, meta)
+    if labels.dtype != torch.uint8 or meta.dtype != torch.int64 or meta.dim() != 2 or meta.shape[1] != 4:
+        raise ValueError("patch_index: uint8 labels and an int64 (N, 4) meta")
+    labels, meta = labels.contiguous(), meta.contiguous()
+    N, K = meta.shape[0], int(num_classes)
+    rows = torch.empty(int(entries), dtype=torch.int32, device=labels.device)
+    _launch("patch_index", lambda: lib().csu_patch_index(N, K, int(max_h), ptr(labels), ptr(meta), ptr(rows),
+                                                         stream_ptr(labels.device)),
+            0, labels.numel() + 8 * rows.numel(), prec="f32")
+    return rows
+
+
+def _snap_ok(snap, what):
+    if snap.dtype != torch.int64 or snap.numel() != 2:
+        raise ValueError(f"{what}: snap is an int64 [seed, counter] snapshot (csu.rng)")
+
+
+def patch_draw(pool, Ph: int, Pw: int, B: int, snap: torch.Tensor, fg_slots: int = 0, p_fg: float = 0.0,
+               class_mask: Optional[int] = None, indices: Optional[torch.Tensor] = None,
+               site: Optional[int] = None) -> torch.Tensor:
+    """csu_patch_draw: the int32 (B, PATCH_RECORD) record {n, cls, cy, cx, oy, ox, fg, count, w0..w7} of B patches
+    of `pool` (a csu.patches.PatchPool) under the snapshot; nothing crosses to the host.  class_mask: bit c set =
+    class c may be a centre (default: every class but 0); indices: int32 (B,) images instead of drawn ones."""
+    from . import rng
+    require_device(snap, indices)
+    _snap_ok(snap, "patch_draw")
+    B, K = int(B), pool.num_classes
+    if class_mask is None:
+        class_mask = (1 << max(K, 2)) - 2
+    if indices is not None:
+        if indices.dtype != torch.int32 or tuple(indices.shape) != (B,):
+            raise ValueError("patch_draw: indices is int32 (B,)")
+        indices = indices.contiguous()
+    site = rng.SITE_PATCH_DRAW if site is None else int(site)
+    record = torch.empty(B, PATCH_RECORD, dtype=torch.int32, device=snap.device)
+    _launch("patch_draw", lambda: lib().csu_patch_draw(ptr(pool.labels), ptr(pool.meta), ptr(pool.rows), pool.N, K,
+                                                       int(class_mask) & 0xFFFFFFFF, int(Ph), int(Pw), B, int(fg_slots),
+                                                       float(p_fg), ptr(indices), ptr(snap), site, ptr(record),
+                                                       stream_ptr(snap.device)),
+            0, 4 * record.numel(), prec="f32")
+    return record
+
+
+def patch_locate(pool, n: torch.Tensor, cls: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """csu_patch_locate: int32 (M, 2) {y, x} of the r[i]-th pixel (raster order) of class cls[i] in image n[i] of
+    `pool`; {-1, -1} where the rank is not below the class's count.  n, cls, r: int32 (M,) on the device."""
+    require_device(n, cls, r)
+    M = n.numel()
+    if any(t.dtype != torch.int32 or tuple(t.shape) != (M,) for t in (n, cls, r)) or M < 1:
+        raise ValueError("patch_locate: n, cls and r are int32 (M,), M >= 1")
+    n, cls, r = n.contiguous(), cls.contiguous(), r.contiguous()
+    yx = torch.empty(M, 2, dtype=torch.int32, device=n.device)
+    _launch("patch_locate", lambda: lib().csu_patch_locate(ptr(pool.labels), ptr(pool.meta), ptr(pool.rows), pool.N,
+                                                           pool.num_classes, M, ptr(n), ptr(cls), ptr(r), ptr(yx),
+                                                           stream_ptr(n.device)),
+            0, 20 * M, prec="f32")
+    return yx
+
+
+def patch_warp(pool, record: torch.Tensor, Ph: int, Pw: int, table: torch.Tensor, ctrl: Optional[torch.Tensor] = None,
+               spacing: int = 0, snap: Optional[torch.Tensor] = None, border: str = "constant", image_fill: float = 0.0,
+               pad_label: int = 0, mask_mode: str = "bilinear", out: str = "binary",
+               noise_site: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """csu_patch_warp: augment_warp with a per-slot source: slot b is the Ph x Pw patch of image record[b, 0] of
+    `pool` with its top-left at (record[b, 4], record[b, 5]) = (oy, ox), warped through row b of `table` / `ctrl`
+    (drawn for Ph x Pw) -> fp32 (B, 3, Ph, Pw) and the mask as augment_warp returns it.  snap: the noise's
+    snapshot (None: no noise)."""
+    from . import rng
+    from .augment import control_grid
+    require_device(record, table, ctrl, snap)
+    Ph, Pw = int(Ph), int(Pw)
+    if record.dtype != torch.int32 or record.dim() != 2 or record.shape[1] != PATCH_RECORD:
+        raise ValueError(f"patch_warp: record is int32 (B, {PATCH_RECORD})")
+    B = record.shape[0]
+    if table.dtype != torch.float32 or tuple(table.shape) != (B, AUGMENT_P):
+        raise ValueError(f"patch_warp: table is fp32 (B, {AUGMENT_P})")
+    if border not in AUGMENT_BORDERS or (mask_mode, out) not in AUGMENT_MASK_MODES:
+        raise ValueError("patch_warp: border constant / replicate; mask_mode bilinear / nearest; out binary, or labels "
+                         "with nearest")
+    if not 0 <= int(pad_label) <= 255 and out != "labels":
+        raise ValueError("patch_warp: pad_label outside 0..255 needs out='labels'")
+    if ctrl is not None:
+        spacing = int(spacing)
+        if spacing < 4 or ctrl.dtype != torch.float32 or tuple(ctrl.shape) != (B, 2) + control_grid(Ph, Pw, spacing):
+            raise ValueError("patch_warp: ctrl is fp32 (B, 2, ceil(Ph / spacing) + 3, ceil(Pw / spacing) + 3), spacing >= 4")
+        ctrl = ctrl.contiguous()
+    if snap is not None:
+        _snap_ok(snap, "patch_warp")
+    rec, tab = record.contiguous(), table.contiguous()
+    mode = AUGMENT_MASK_MODES[(mask_mode, out)]
+    oimg = torch.empty(B, 3, Ph, Pw, dtype=torch.float32, device=rec.device)
+    if out == "labels":
+        om = torch.empty(B, Ph, Pw, dtype=torch.int64, device=rec.device)
+    else:
+        om = torch.empty(B, 1, Ph, Pw, dtype=torch.float32, device=rec.device)
+    site = rng.SITE_AUGMENT_NOISE if noise_site is None else int(noise_site)
+    _launch("patch_warp", lambda: lib().csu_patch_warp(B, Ph, Pw, pool.N, ptr(pool.pixels), ptr(pool.labels), ptr(pool.meta),
+                                                       ptr(pool.mean), ptr(rec), ptr(tab), ptr(ctrl), int(spacing), ptr(snap),
+                                                       site, AUGMENT_BORDERS[border], float(image_fill), int(pad_label), mode,
+                                                       ptr(oimg), ptr(om), stream_ptr(rec.device)),
+            0, B * Ph * Pw * (4 + 12 + om.element_size()), prec="f32")
+    return oimg, om
+
+
 def shared_cast(x: torch.Tensor, dtype: torch.dtype):
     """(xc, xc) -- the same `dtype` copy of x for two consumers (see _SharedCastFn)."""
     return _SharedCastFn.apply(x, dtype)

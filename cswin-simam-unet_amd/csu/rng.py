@@ -39,6 +39,7 @@ OFF_DROPPATH_MLP = 5
 SITE_AUGMENT_DRAW = 4080      # the per-image parameter table
 SITE_AUGMENT_CTRL = 4081      # the elastic control displacements
 SITE_AUGMENT_NOISE = 4082     # the per-pixel Gaussian noise
+SITE_PATCH_DRAW = 4083        # csu.patches: the image, class, pixel and origin of a patch
 
 
 def _dev(device) -> torch.device:

@@ -1024,6 +1024,66 @@ int csu_augment_warp(int B, int H, int W, const void* img, const void* mask, con
                      float image_fill, int pad_label, int mask_mode, float* out_img, void* out_mask, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Patch pool: training patches cut on the device from full-size cases kept in HBM (csrc/patch.hip, the warp
+ * in csrc/augment_warp.hip).  The reference has no counterpart; this is nnU-Net's patch sampling with forced
+ * foreground centres.
+ *
+ * The pool of N cases (N <= 2^20, each H_i, W_i <= 2^24 and H_i W_i < 2^31):
+ *   pixels  uint8, the images HWC (3 bytes per pixel), cases back to back
+ *   labels  uint8, one byte per pixel, the same order
+ *   meta    int64 [N][4] = {pixel offset (image i starts at pixels + 3 offset and labels + offset), H_i, W_i,
+ *           row-table offset (in int32 entries into rows)}
+ *   mean    float [N]: csu_augment_mean of each image, the mean the contrast step of a patch of it uses
+ *   rows    int32: for image i, class c in 0..Kc-1 and y in 0..H_i,
+ *           rows[meta[i][3] + c (H_i + 1) + y] = the number of pixels of class c in rows [0, y) of image i (an
+ *           exclusive prefix over rows: the entry at H_i is the class's pixel count); Kc (H_i + 1) entries per image.
+ * Classes: K = 1 is the binary case, Kc = 2, class = (label > 0).  Otherwise 2 <= K <= 32, Kc = K, class = label,
+ * and a label >= K (an ignore value) belongs to no class.
+ *
+ * csu_patch_index fills rows (integers only: deterministic).  max_h, the largest H_i, only sizes the launch.
+ *
+ * csu_patch_draw: record[b], int32 [B][CSU_PATCH_RECORD] = {n, cls, cy, cx, oy, ox, fg, count, w0..w7}, a pure
+ * function of (seed, counter, site, b), the pool and the arguments -- not of B.  w0..w3 / w4..w7 are the words of
+ * the Philox4x32-7 calls j = 0 / 1 with counter words {j, (b << 12) ^ site, counter} (the scheme of
+ * csu_augment_draw), stored as their bit patterns.  pick(w, m) = (uint64(w) m) >> 32; u01(w) = (w >> 8) / 2^24.
+ *   image   n = indices[b] clamped to 0..N-1 when indices is not NULL, else pick(w0, N)
+ *   foreground iff b < fg_slots or u01(w1) < p_fg
+ *   class   of the classes c < Kc with bit c of class_mask set and a nonzero count in image n, m of them in
+ *           ascending order, the pick(w2, m)-th; m = 0: the slot becomes a uniform one
+ *   pixel   count = that class's pixels in image n, r = pick(w3, count), (cy, cx) = the r-th pixel of the class
+ *           in raster order
+ *   origin  per axis (L the image's extent, P the patch's, c the centre): L < P: -((P - L) / 2) (centred, the rest
+ *           is padding); else foreground: min(max(c - P / 2, 0), L - P); uniform: pick(w4, H - Ph + 1) for oy,
+ *           pick(w5, W - Pw + 1) for ox.  Integer divisions of non-negative values.
+ *   A uniform slot (not foreground, or no eligible class) has cls = cy = cx = -1, fg = 0, count = 0; fg = 1 marks
+ *   a slot centred on (cy, cx).
+ * csu_patch_locate: yx[i] = {y, x} of the r[i]-th pixel (raster order) of class cls[i] in image n[i], or {-1, -1}
+ * when n, cls or r is out of range (r >= count).  The same device function as the draw's.
+ *
+ * csu_patch_warp: csu_augment_warp with a per-slot source.  The output is Ph x Pw; slot b reads image
+ * n = record[b][0] (clamped to 0..N-1) with origin (ox, oy) = (record[b][5], record[b][4]) (clamped to +-2^24)
+ * and mean[n].  table / ctrl are those of csu_augment_draw(cfg, B, Ph, Pw, ...): A, the B-spline field and the
+ * noise index y Pw + x live in the patch frame.  The source position of output pixel p is (ox, oy) + A(p + d(p)):
+ * s = A(p + d) is evaluated in fp32 in the patch frame as csu_augment_warp does, clamped to [-2 - o, L + 1 - o]
+ * (constant border) or [-o, L - 1 - o] (replicate) per axis, floor / fraction / nearest rounding are taken there,
+ * and the INTEGER origin is added to the integer tap coordinates: the result does not depend on where in a large
+ * image the patch lies, and an integer table gives the exact slice.  Border rules (against the image n, not the
+ * pool), image_fill, pad_label, mask modes, the intensity chain and the noise are csu_augment_warp's; with
+ * origin 0 and Ph x Pw = H x W the two agree bit for bit.
+ * ------------------------------------------------------------------------------------- */
+#define CSU_PATCH_RECORD 16
+int csu_patch_index(int N, int K, int max_h, const void* labels, const int64_t* meta, int32_t* rows, void* stream);
+int csu_patch_draw(const void* labels, const int64_t* meta, const int32_t* rows, int N, int K, unsigned class_mask, int Ph,
+                   int Pw, int B, int fg_slots, float p_fg, const int32_t* indices, const uint64_t* rng, unsigned site,
+                   int32_t* record, void* stream);
+int csu_patch_locate(const void* labels, const int64_t* meta, const int32_t* rows, int N, int K, int M, const int32_t* n,
+                     const int32_t* cls, const int32_t* r, int32_t* yx, void* stream);
+int csu_patch_warp(int B, int Ph, int Pw, int N, const void* pixels, const void* labels, const int64_t* meta,
+                   const float* mean, const int32_t* record, const float* table, const float* ctrl, int spacing,
+                   const uint64_t* rng, unsigned noise_site, int border, float image_fill, int pad_label, int mask_mode,
+                   float* out_img, void* out_mask, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Tiled whole-image inference (csrc/tile.hip): sliding-window prediction of an H x W image with a
  * network of fixed S x S input, with test-time augmentation.  The reference has no counterpart.
  *   table: int32 (B, 6) on the device, one record per batch slot: {y0, x0, hflip, vflip, clockwise
