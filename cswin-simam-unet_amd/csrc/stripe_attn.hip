@@ -24,6 +24,7 @@
 //   The split kernels (stripe_fwd_w, stripe_bwd_dq_w / _dkdv_w) run wsplit() workgroups per
 //   window-head: enough for about 1024 workgroups per launch, each with at least 128 rows.  An even
 //   split runs as NW = 8 (two partners merged into one 8-wave workgroup), an odd one as NW = 4.
+//   csu_stripe_args.split forces the factor; csu_stripe_attn_plan reports every choice of this map.
 #include <cstdlib>
 
 #include "common.hpp"
@@ -1148,8 +1149,9 @@ __global__ __launch_bounds__(64 * NW) void stripe_bwd_dq_w(csu_stripe_args a, in
     const int rows = (((npad + split - 1) / split) + 31) & ~31;   // 32-aligned: mask groups start on 8
     const int qbeg = w.blk * rows, qend = min(npad, qbeg + rows);
     // the wave's query-block operands (Q, dO and O fragments, lse): the first block's are loaded
-    // with the staging loads, so their latency overlaps the K/V staging; later blocks (only when a
-    // workgroup owns > 128 query rows: the 1024x1024 stages) load at the top of their iteration
+    // with the staging loads, so their latency overlaps the K/V staging; later blocks (when a workgroup
+    // owns more than 32 * NW query rows, i.e. 128 or 256: chosen by the split, so by the batch size, at
+    // every image size -- window_plan's passes > 1) load at the top of their iteration
     Frag<bf16> qf, gf, of;
     float lq_raw;
     const __amdgpu_buffer_rsrc_t rs_img = buf_rsrc(img, (long)L * C3 * 2), rs_g = buf_rsrc(gimg, (long)L * C * 2),
@@ -1252,8 +1254,9 @@ __global__ __launch_bounds__(64 * NW) void stripe_bwd_dkdv_w(csu_stripe_args a, 
     const int rows = (((npad + split - 1) / split) + 31) & ~31;   // 32-aligned: mask groups start on 8
     const int kbeg = w.blk * rows, kend = min(npad, kbeg + rows);
     // the wave's key-block fragments: the first block's are loaded with the staging loads; later
-    // blocks (only when a workgroup owns > 128 key rows: the 1024x1024 stages) load at the top of
-    // their iteration -- no second register set, so the kernel stays at <= 128 VGPRs (4 waves/SIMD)
+    // blocks (when a workgroup owns more than 32 * NW key rows, i.e. 128 or 256: chosen by the split, so
+    // by the batch size -- window_plan's passes > 1) load at the top of their iteration -- no second
+    // register set, so the kernel stays at <= 128 VGPRs (4 waves/SIMD)
     Frag<bf16> kf, vf;
     const __amdgpu_buffer_rsrc_t rs_img = buf_rsrc(img, (long)L * C3 * 2);
     {
@@ -1830,13 +1833,9 @@ Geo geo_of(const csu_stripe_args& a) {
     const csu_stripe_branch& g = a.br[0];
     return {g.H_sp * g.W_sp, (a.reso / g.H_sp) * (a.reso / g.W_sp)};
 }
-// grid of k workgroups per (image, window, head); the streamed kernels take one per 128-row block
+// grid of k workgroups per (image, window, head); the streamed kernels take one per 128-row block (streamed_plan)
 dim3 wgrid(const csu_stripe_args& a, int k) { return dim3(a.B * geo_of(a).nwin * a.heads * k, a.nbranch); }
-dim3 grid_of(const csu_stripe_args& a) { return wgrid(a, (geo_of(a).N + QR - 1) / QR); }
 
-// the one-pass backward handles the launch (bf16, window <= 512 tokens: WM = 512 holds the four
-// window images in 128 KiB of LDS, one workgroup per CU)
-bool use_fused_bwd(const csu_stripe_args& a, int dtype) { return dtype == CSU_BF16 && geo_of(a).N <= 512; }
 int fused_nblk(const csu_stripe_args& a) { return a.B * geo_of(a).nwin; }
 
 template <int WM, int NW = 4>
@@ -1847,26 +1846,27 @@ void bwd_fused(const csu_stripe_args& a, const bf16* qkv, const bf16* out, const
     });
 }
 
+// ---- The launch plan.  plan_of() takes every decision of this layer once -- kernel family, LDS image
+// size, split, waves, the LePE weight-gradient kernel and its blocking, the workspace -- and the
+// launches below read them from it; csu_stripe_attn_plan returns the same struct, so what it reports
+// is what runs.  (The split kernels derive a workgroup's rows from the launched split by the formula
+// of window_plan.)
+
 // split factor of the whole-window kernels: workgroups per window-head, so that a launch has
 // about 1024 workgroups, each owning at least 128 query (key) rows -- one 32-row pass per wave
-// (512x512: 2 at stages 3/4; 1024x1024: 4 at stage 3 (N = 512), 8 at stage 4 (N = 1024))
+// (512x512: 2 at stages 3/4; 1024x1024: 4 at stage 3 (N = 512), 8 at stage 4 (N = 1024)).
+// args.split != 0 (validate: 1 .. max_split) replaces the heuristic
 #ifndef ATTN_SPLIT_WGS
 #define ATTN_SPLIT_WGS 1024
 #endif
+int max_split(int N) { return (((N + 31) & ~31) + 127) / 128; }
 int wsplit(const csu_stripe_args& a) {
     const Geo w = geo_of(a);
     const long wgs = (long)a.B * w.nwin * a.heads * a.nbranch;
-    const int maxsp = (((w.N + 31) & ~31) + 127) / 128;
+    const int maxsp = max_split(w.N);
+    if (a.split >= 1 && a.split <= maxsp) return a.split;
     const long want = (ATTN_SPLIT_WGS + wgs - 1) / wgs;
     return (int)(want < maxsp ? want : maxsp);
-}
-
-bool use_window_path(const csu_stripe_args& a, int dtype) { return dtype == CSU_BF16 && geo_of(a).N <= WMAX; }
-
-// LDS image rows of a forward launch: the window rounded up to 256 / 512 / 1024 tokens
-int wm_of(const csu_stripe_args& a) {
-    const int N = geo_of(a).N;
-    return N <= 256 ? 256 : N <= 512 ? 512 : 1024;
 }
 
 // ATTN_FWD_WAVES = 8: the forward's split partners merged into one 8-wave workgroup (the window's
@@ -1877,35 +1877,124 @@ int wm_of(const csu_stripe_args& a) {
 #ifndef ATTN_BWD_WAVES
 #define ATTN_BWD_WAVES 8
 #endif
+
+// a split whole-window kernel: an even split runs as 8-wave workgroups (merge8), an odd one as 4-wave
+// ones; each owns `rows` rows of the padded window and walks them in passes of 32 * waves
+csu_stripe_kernel_plan window_plan(int wm, int sp, bool merge8, int N) {
+    csu_stripe_kernel_plan p = {};
+    const int npad = (N + 31) & ~31;
+    p.kernel = CSU_STRIPE_WINDOW;
+    p.wm = wm;
+    p.sp = sp;
+    p.waves = merge8 && sp % 2 == 0 ? 8 : 4;
+    p.split = p.waves == 8 ? sp / 2 : sp;
+    p.rows = (((npad + p.split - 1) / p.split) + 31) & ~31;
+    const int step = 32 * p.waves;
+    for (int blk = 0; blk < p.split; ++blk) {
+        const int left = npad - blk * p.rows, own = left < p.rows ? left : p.rows;
+        if (own <= 0) {
+            p.flags |= CSU_PLAN_EMPTY_PARTNER;
+            continue;
+        }
+        const int n = (own + step - 1) / step;
+        p.passes = p.passes > n ? p.passes : n;
+        if (n > 1 && own % step) p.flags |= CSU_PLAN_RAGGED_PASS;
+    }
+    return p;
+}
+
+csu_stripe_kernel_plan streamed_plan(int N) {
+    csu_stripe_kernel_plan p = {};
+    p.kernel = CSU_STRIPE_STREAMED;
+    p.sp = 1;
+    p.split = (N + QR - 1) / QR;
+    p.waves = NT / 64;
+    p.rows = QR;
+    p.passes = 1;
+    return p;
+}
+
+// the one-pass backward (bf16, window <= 512 tokens: WM = 512 holds the four window images in
+// 128 KiB of LDS, one workgroup per CU)
+csu_stripe_kernel_plan fused_bwd_plan(int N) {
+    csu_stripe_kernel_plan p = {};
+    p.kernel = CSU_STRIPE_FUSED_BWD;
+    p.wm = N <= 128 ? 128 : N <= 256 ? 256 : 512;
+    p.waves = p.wm == 512 ? 8 : 4;
+    p.sp = p.split = 1;
+    p.rows = p.wm;
+    p.passes = p.wm / (32 * p.waves);
+    return p;
+}
+
+// stand-alone pass 1 of the LePE weight gradient (tiled kernel if its tile fits, else untiled)
+void wgrad_plan(const csu_stripe_args& a, int dtype, csu_stripe_plan& p) {
+    const int ty = lepe_tile_rows(a, dtype);
+    if (!ty) {
+        p.wgrad_kernel = CSU_LEPE_PARTIAL;
+        p.wgrad_nblk = wgrad_blocks(a);
+        p.tile_rows = p.rows_blk = p.tiles_blk = p.wgrad_flags = 0;
+        return;
+    }
+    const int rb = lepe_rows_blk(a, ty);
+    p.wgrad_kernel = CSU_LEPE_TILES;
+    p.tile_rows = ty;
+    p.rows_blk = rb;
+    p.tiles_blk = rb / ty;
+    p.wgrad_nblk = a.B * ((a.reso + rb - 1) / rb);
+    p.wgrad_flags = (a.reso % rb ? 1 : 0) | (a.reso % ty ? 2 : 0);
+}
+
+csu_stripe_plan plan_of(const csu_stripe_args& a, int dtype) {
+    csu_stripe_plan p = {};
+    const int N = geo_of(a).N;
+    const bool window = dtype == CSU_BF16 && N <= WMAX;   // the whole window fits the LDS images
+    const bool fused = dtype == CSU_BF16 && N <= 512;
+    const int sp = window ? wsplit(a) : 1;
+    // LDS image rows of a forward launch: the window rounded up to 256 / 512 / 1024 tokens
+    p.fwd = window ? window_plan(N <= 256 ? 256 : N <= 512 ? 512 : 1024, sp, ATTN_FWD_WAVES == 8, N) : streamed_plan(N);
+    // the split backward serves only windows of 513..1024 tokens, so its LDS images always have WMAX rows
+    p.bwd = fused ? fused_bwd_plan(N) : window ? window_plan(WMAX, sp, ATTN_BWD_WAVES == 8, N) : streamed_plan(N);
+    // workspace: enough partial blocks for either dtype's layout (the dtype is decided at launch)
+    int n = wgrad_blocks(a);
+    n = n > fused_nblk(a) ? n : fused_nblk(a);
+    for (int dt : {CSU_BF16, CSU_F32}) {
+        wgrad_plan(a, dt, p);
+        n = n > p.wgrad_nblk ? n : p.wgrad_nblk;
+    }
+    p.ws_blocks = n;
+    wgrad_plan(a, dtype, p);
+    p.lepe_kernel = fused ? (int)CSU_LEPE_IN_FUSED_BWD : p.wgrad_kernel;
+    p.lepe_nblk = fused ? fused_nblk(a) : p.wgrad_nblk;
+    return p;
+}
+
 template <int WM>
-void fwd_w(const csu_stripe_args& a, const bf16* qkv, bf16* out, float* lse, hipStream_t st) {
-    const int sp = wsplit(a);
+void fwd_w(const csu_stripe_args& a, const csu_stripe_kernel_plan& k, const bf16* qkv, bf16* out, float* lse, hipStream_t st) {
     with_flag(a.drop_p > 0.f, [&](auto df) {
         constexpr bool D = decltype(df)::value;
-        if (ATTN_FWD_WAVES == 8 && sp % 2 == 0)
-            stripe_fwd_w<WM, D, 8><<<wgrid(a, sp / 2), 512, 0, st>>>(a, sp / 2, qkv, out, lse);
+        if (k.waves == 8)
+            stripe_fwd_w<WM, D, 8><<<wgrid(a, k.split), 512, 0, st>>>(a, k.split, qkv, out, lse);
         else
-            stripe_fwd_w<WM, D><<<wgrid(a, sp), NT, 0, st>>>(a, sp, qkv, out, lse);
+            stripe_fwd_w<WM, D><<<wgrid(a, k.split), NT, 0, st>>>(a, k.split, qkv, out, lse);
     });
 }
 
 // The split whole-window backward.  Only windows of 513..1024 tokens get here (windows of at most 512
-// tokens take stripe_bwd_fused_w: use_fused_bwd), so the LDS images always have WMAX rows.  Their
+// tokens take stripe_bwd_fused_w: plan_of), so the LDS images always have WMAX rows.  Their
 // K / V or Q / dO images bound residency: split partners merged into 8-wave workgroups, as the
 // forward (ATTN_FWD_WAVES)
-void bwd_w(const csu_stripe_args& a, const bf16* qkv, const bf16* out, const bf16* dout, const float* lse, float* delta,
-           bf16* dqkv, hipStream_t st) {
-    const int sp = wsplit(a);
+void bwd_w(const csu_stripe_args& a, const csu_stripe_kernel_plan& k, const bf16* qkv, const bf16* out, const bf16* dout,
+           const float* lse, float* delta, bf16* dqkv, hipStream_t st) {
+    const dim3 g = wgrid(a, k.split);
     with_flag(a.drop_p > 0.f, [&](auto df) {
         constexpr bool D = decltype(df)::value;
-        if (ATTN_BWD_WAVES == 8 && sp % 2 == 0) {
-            const dim3 g = wgrid(a, sp / 2);
-            stripe_bwd_dq_w<WMAX, D, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, out, dout, lse, delta, dqkv);
-            stripe_bwd_dkdv_w<WMAX, D, 8><<<g, 512, 0, st>>>(a, sp / 2, qkv, dout, lse, delta, dqkv);
+        if (k.waves == 8) {
+            stripe_bwd_dq_w<WMAX, D, 8><<<g, 512, 0, st>>>(a, k.split, qkv, out, dout, lse, delta, dqkv);
+            stripe_bwd_dkdv_w<WMAX, D, 8><<<g, 512, 0, st>>>(a, k.split, qkv, dout, lse, delta, dqkv);
         } else {
-            const dim3 g = wgrid(a, sp);
-            stripe_bwd_dq_w<WMAX, D><<<g, NT, 0, st>>>(a, sp, qkv, out, dout, lse, delta, dqkv);
-            stripe_bwd_dkdv_w<WMAX, D><<<g, NT, 0, st>>>(a, sp, qkv, dout, lse, delta, dqkv);
+            stripe_bwd_dq_w<WMAX, D><<<g, NT, 0, st>>>(a, k.split, qkv, out, dout, lse, delta, dqkv);
+            stripe_bwd_dkdv_w<WMAX, D><<<g, NT, 0, st>>>(a, k.split, qkv, dout, lse, delta, dqkv);
         }
     });
 }
@@ -1931,20 +2020,22 @@ int validate(const csu_stripe_args* a, int dtype) {
         return fail(CSU_E_UNSUPPORTED, "stripe_attn: windows of <= 4096 tokens, <= 1024 wide");
     if (a->drop_p < 0.f || a->drop_p >= 1.f || (a->drop_p > 0.f && !a->drop_rng))
         return fail(CSU_E_ARG, "stripe_attn: attention dropout needs 0 <= p < 1 and an RNG snapshot");
+    if (a->split < 0 || a->split > max_split(a->br[0].H_sp * a->br[0].W_sp))
+        return fail(CSU_E_ARG, "stripe_attn: split must be 0 (heuristic) or 1 .. ceil(roundup32(N) / 128)");
     return 0;
 }
 
 template <typename T>
-void fwd_generic(const csu_stripe_args& a, const void* qkv, void* out, float* lse, hipStream_t st) {
+void fwd_generic(const csu_stripe_args& a, const csu_stripe_kernel_plan& k, const void* qkv, void* out, float* lse, hipStream_t st) {
     with_flag(a.drop_p > 0.f, [&](auto df) {
-        stripe_fwd<T, decltype(df)::value><<<grid_of(a), NT, 0, st>>>(a, (const T*)qkv, (T*)out, lse);
+        stripe_fwd<T, decltype(df)::value><<<wgrid(a, k.split), NT, 0, st>>>(a, (const T*)qkv, (T*)out, lse);
     });
 }
 
 template <typename T>
-void bwd_generic(const csu_stripe_args& a, const void* qkv, const void* out, const void* dout, const float* lse,
-                 float* delta, void* dqkv, hipStream_t st) {
-    const dim3 grid = grid_of(a);
+void bwd_generic(const csu_stripe_args& a, const csu_stripe_kernel_plan& k, const void* qkv, const void* out, const void* dout,
+                 const float* lse, float* delta, void* dqkv, hipStream_t st) {
+    const dim3 grid = wgrid(a, k.split);
     with_flag(a.drop_p > 0.f, [&](auto df) {
         constexpr bool D = decltype(df)::value;
         stripe_bwd_dq<T, D><<<grid, NT, 0, st>>>(a, (const T*)qkv, (const T*)out, (const T*)dout, lse, delta, (T*)dqkv);
@@ -1971,26 +2062,26 @@ extern "C" int csu_stripe_attn_fwd(const csu_stripe_args* a, int dtype, const vo
     if (int e = validate(a, dtype)) return e;
     if (!qkv || !out || !lse) return fail(CSU_E_ARG, "stripe_attn_fwd: null buffer");
     const hipStream_t st = as_stream(stream);
-    if (use_window_path(*a, dtype)) {
-        switch (wm_of(*a)) {
-            case 256: fwd_w<256>(*a, (const bf16*)qkv, (bf16*)out, lse, st); break;
-            case 512: fwd_w<512>(*a, (const bf16*)qkv, (bf16*)out, lse, st); break;
-            default: fwd_w<1024>(*a, (const bf16*)qkv, (bf16*)out, lse, st); break;
+    const csu_stripe_kernel_plan k = plan_of(*a, dtype).fwd;
+    if (k.kernel == CSU_STRIPE_WINDOW) {
+        switch (k.wm) {
+            case 256: fwd_w<256>(*a, k, (const bf16*)qkv, (bf16*)out, lse, st); break;
+            case 512: fwd_w<512>(*a, k, (const bf16*)qkv, (bf16*)out, lse, st); break;
+            default: fwd_w<1024>(*a, k, (const bf16*)qkv, (bf16*)out, lse, st); break;
         }
     } else if (dtype == CSU_BF16) {
-        fwd_generic<bf16>(*a, qkv, out, lse, st);
+        fwd_generic<bf16>(*a, k, qkv, out, lse, st);
     } else {
-        fwd_generic<float>(*a, qkv, out, lse, st);
+        fwd_generic<float>(*a, k, qkv, out, lse, st);
     }
     return check_launch("stripe_attn_fwd");
 }
 
-// LePE weight-gradient partial blocks of a launch (tiled kernel if its tile fits, else untiled)
-int lepe_nblk(const csu_stripe_args& a, int dtype) {
-    const int ty = lepe_tile_rows(a, dtype);
-    if (!ty) return wgrad_blocks(a);
-    const int rb = lepe_rows_blk(a, ty);
-    return a.B * ((a.reso + rb - 1) / rb);
+extern "C" int csu_stripe_attn_plan(const csu_stripe_args* a, int dtype, csu_stripe_plan* out) {
+    if (int e = validate(a, dtype)) return e;
+    if (!out) return fail(CSU_E_ARG, "stripe_attn_plan: null plan");
+    *out = plan_of(*a, dtype);
+    return 0;
 }
 
 // many LePE weight-gradient reductions in one launch (the end-of-backward batch): item table in the
@@ -2057,14 +2148,14 @@ void lepe_reduce_inline(const csu_stripe_args& a, int nblk, const float* part, h
 }
 
 // pass 1 (block partials) for the launches whose attention backward does not form them itself
-void lepe_wgrad_launch(const csu_stripe_args& a, int dtype, const void* qkv, const void* dout, float* part, hipStream_t st) {
-    const int ty = lepe_tile_rows(a, dtype);
-    const int nblk = lepe_nblk(a, dtype);
-    if (ty) {
+void lepe_wgrad_launch(const csu_stripe_args& a, const csu_stripe_plan& p, int dtype, const void* qkv, const void* dout,
+                       float* part, hipStream_t st) {
+    const int ty = p.tile_rows, nblk = p.wgrad_nblk;
+    if (p.wgrad_kernel == CSU_LEPE_TILES) {
         const size_t es = dtype == CSU_BF16 ? 2 : 4;
         const size_t lds = (size_t)(2 * ty + 2) * a.reso * HD * es;
         const dim3 g((unsigned)nblk, (unsigned)a.heads, (unsigned)a.nbranch);
-        const int rb = lepe_rows_blk(a, ty);
+        const int rb = p.rows_blk;
         if (dtype == CSU_BF16) lepe_wgrad_tiles<bf16><<<g, NT, lds, st>>>(a, ty, rb, (const bf16*)qkv, (const bf16*)dout, part);
         else lepe_wgrad_tiles<float><<<g, NT, lds, st>>>(a, ty, rb, (const float*)qkv, (const float*)dout, part);
     } else if (dtype == CSU_BF16) {
@@ -2077,16 +2168,13 @@ void lepe_wgrad_launch(const csu_stripe_args& a, int dtype, const void* qkv, con
 extern "C" size_t csu_stripe_attn_bwd_workspace(const csu_stripe_args* a) {
     if (!a) return 0;
     // enough for either partial layout (dtype decided at launch)
-    int n = wgrad_blocks(*a);
-    for (int dt : {CSU_BF16, CSU_F32}) n = n > lepe_nblk(*a, dt) ? n : lepe_nblk(*a, dt);
-    n = n > fused_nblk(*a) ? n : fused_nblk(*a);
-    return (size_t)a->nbranch * n * a->heads * HD * 10 * sizeof(float);
+    return (size_t)a->nbranch * plan_of(*a, CSU_BF16).ws_blocks * a->heads * HD * 10 * sizeof(float);
 }
 
 // partial blocks csu_stripe_attn_bwd_ex(lepe_deferred = 1) leaves in its workspace
 extern "C" int csu_stripe_lepe_nblk(const csu_stripe_args* a, int dtype) {
     if (!a) return 0;
-    return use_fused_bwd(*a, dtype) ? fused_nblk(*a) : lepe_nblk(*a, dtype);
+    return plan_of(*a, dtype).lepe_nblk;
 }
 
 extern "C" int csu_stripe_lepe_reduce_batch(const csu_lepe_reduce_item* items, int count, void* stream) {
@@ -2116,22 +2204,22 @@ extern "C" int csu_stripe_attn_bwd_ex(const csu_stripe_args* a, int dtype, const
     if (int e = check_lepe_layout(*a, "stripe_attn_bwd")) return e;
     const hipStream_t st = as_stream(stream);
     float* part = (float*)workspace;
-    if (use_fused_bwd(*a, dtype)) {
+    const csu_stripe_plan p = plan_of(*a, dtype);
+    if (p.bwd.kernel == CSU_STRIPE_FUSED_BWD) {
         // one pass: dQ, dK, dV and (do_lepe) the LePE weight-gradient partials, reduced below or deferred
         const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *go = (const bf16*)dout;
         float* pp = do_lepe ? part : nullptr;
-        const int N = geo_of(*a).N;
-        if (N <= 128) bwd_fused<128>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
-        else if (N <= 256) bwd_fused<256>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
+        if (p.bwd.wm == 128) bwd_fused<128>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
+        else if (p.bwd.wm == 256) bwd_fused<256>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
         else bwd_fused<512, 8>(*a, q, o, go, lse, (bf16*)dqkv, pp, st);
     } else {
-        if (use_window_path(*a, dtype))
-            bwd_w(*a, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, st);
-        else if (dtype == CSU_BF16) bwd_generic<bf16>(*a, qkv, out, dout, lse, delta, dqkv, st);
-        else bwd_generic<float>(*a, qkv, out, dout, lse, delta, dqkv, st);
-        if (do_lepe) lepe_wgrad_launch(*a, dtype, qkv, dout, part, st);
+        if (p.bwd.kernel == CSU_STRIPE_WINDOW)
+            bwd_w(*a, p.bwd, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, st);
+        else if (dtype == CSU_BF16) bwd_generic<bf16>(*a, p.bwd, qkv, out, dout, lse, delta, dqkv, st);
+        else bwd_generic<float>(*a, p.bwd, qkv, out, dout, lse, delta, dqkv, st);
+        if (do_lepe) lepe_wgrad_launch(*a, p, dtype, qkv, dout, part, st);
     }
-    if (do_lepe && !lepe_deferred) lepe_reduce_inline(*a, csu_stripe_lepe_nblk(a, dtype), part, st);
+    if (do_lepe && !lepe_deferred) lepe_reduce_inline(*a, p.lepe_nblk, part, st);
     return check_launch("stripe_attn_bwd");
 }
 
@@ -2150,8 +2238,9 @@ extern "C" int csu_stripe_lepe_wgrad(const csu_stripe_args* a, int dtype, const 
     if (workspace_bytes < csu_stripe_attn_bwd_workspace(a) || !workspace)
         return fail(CSU_E_WORKSPACE, "stripe_lepe_wgrad: workspace too small");
     if (int e = check_lepe_layout(*a, "stripe_lepe_wgrad")) return e;
-    lepe_wgrad_launch(*a, dtype, qkv, dout, (float*)workspace, as_stream(stream));
-    lepe_reduce_inline(*a, lepe_nblk(*a, dtype), (const float*)workspace, as_stream(stream));
+    const csu_stripe_plan p = plan_of(*a, dtype);
+    lepe_wgrad_launch(*a, p, dtype, qkv, dout, (float*)workspace, as_stream(stream));
+    lepe_reduce_inline(*a, p.wgrad_nblk, (const float*)workspace, as_stream(stream));
     return check_launch("stripe_lepe_wgrad");
 }
 

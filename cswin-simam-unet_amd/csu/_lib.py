@@ -27,8 +27,26 @@ class StripeBranch(ctypes.Structure):
 
 class StripeArgs(ctypes.Structure):
     _fields_ = [("B", c_int32), ("reso", c_int32), ("C", c_int32), ("heads", c_int32), ("head_dim", c_int32),
-                ("nbranch", c_int32), ("scale", c_float), ("_pad", c_int32), ("br", StripeBranch * 2),
+                ("nbranch", c_int32), ("scale", c_float), ("split", c_int32), ("br", StripeBranch * 2),
                 ("drop_rng", c_void_p), ("drop_site", ctypes.c_uint32), ("drop_p", c_float)]
+
+
+class StripeKernelPlan(ctypes.Structure):
+    """csu_stripe_kernel_plan (include/csu.h)."""
+    _fields_ = [(n, c_int32) for n in ("kernel", "wm", "sp", "split", "waves", "rows", "passes", "flags")]
+
+
+class StripePlan(ctypes.Structure):
+    """csu_stripe_plan (include/csu.h)."""
+    _fields_ = [("fwd", StripeKernelPlan), ("bwd", StripeKernelPlan)] + [
+        (n, c_int32) for n in ("lepe_kernel", "lepe_nblk", "wgrad_kernel", "wgrad_nblk", "tile_rows", "rows_blk",
+                               "tiles_blk", "wgrad_flags", "ws_blocks", "_pad")]
+
+
+# csu_stripe_kernel, csu_lepe_kernel, csu_stripe_plan_flags (include/csu.h)
+STRIPE_STREAMED, STRIPE_WINDOW, STRIPE_FUSED_BWD = 0, 1, 2
+LEPE_IN_FUSED_BWD, LEPE_TILES, LEPE_PARTIAL = 0, 1, 2
+PLAN_RAGGED_PASS, PLAN_EMPTY_PARTNER = 1, 2
 
 
 class LnParamItem(ctypes.Structure):
@@ -209,6 +227,7 @@ _SIGS = {
     "csu_stripe_attn_bwd_ex": (ctypes.c_int, [ctypes.POINTER(StripeArgs), ctypes.c_int, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.c_int, c_void_p]),
     "csu_stripe_lepe_nblk": (ctypes.c_int, [ctypes.POINTER(StripeArgs), ctypes.c_int]),
+    "csu_stripe_attn_plan": (ctypes.c_int, [ctypes.POINTER(StripeArgs), ctypes.c_int, ctypes.POINTER(StripePlan)]),
     "csu_stripe_lepe_reduce_batch": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "csu_linear_wgrad_group_plan": (c_size_t, [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

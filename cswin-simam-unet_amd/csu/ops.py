@@ -32,11 +32,14 @@ def _stripe_fwd_work(geom, B, esize):
 class StripeGeometry:
     """Static description of the attention branches of one CSWinBlock.
 
-    branches: [(H_sp, W_sp, ch_off)] -- geometry per LePEAttention (cswin:232-240)."""
+    branches: [(H_sp, W_sp, ch_off)] -- geometry per LePEAttention (cswin:232-240).
+    split: csu_stripe_args.split, 0 = the launch layer's heuristic (the model never sets it; tests force
+    the other launch plans with it)."""
 
     def __init__(self, reso: int, C: int, heads: int, branches: Sequence[Tuple[int, int, int]], scale: float,
-                 head_dim: int = 32):
+                 head_dim: int = 32, split: int = 0):
         self.reso, self.C, self.heads, self.scale, self.head_dim = reso, C, heads, float(scale), head_dim
+        self.split = int(split)
         self.branches = [tuple(int(v) for v in b) for b in branches]
         if not 1 <= len(self.branches) <= 2:
             raise ValueError("1 or 2 branches")
@@ -51,7 +54,7 @@ class StripeGeometry:
         if drop is not None and drop.p > 0:
             a.drop_rng, a.drop_site, a.drop_p = drop.snap.data_ptr(), drop.site, drop.p
         a.B, a.reso, a.C, a.heads, a.head_dim = B, self.reso, self.C, self.heads, self.head_dim
-        a.nbranch, a.scale = len(self.branches), self.scale
+        a.nbranch, a.scale, a.split = len(self.branches), self.scale, self.split
         for i, (hs, wsp, off) in enumerate(self.branches):
             br = a.br[i]
             br.H_sp, br.W_sp, br.ch_off = hs, wsp, off
@@ -59,6 +62,16 @@ class StripeGeometry:
             if dws is not None:
                 br.lepe_dw, br.lepe_db = dws[i].data_ptr(), dbs[i].data_ptr()
         return a
+
+
+def stripe_plan(geom: StripeGeometry, B: int, dtype: torch.dtype) -> "_lib.StripePlan":
+    """csu_stripe_attn_plan: the launch plan of stripe_attention(geom) at batch B (kernel family, LDS
+    image size, split, waves, passes; the LePE weight-gradient kernel and its blocking).  Host only."""
+    z = torch.zeros(1)   # validate() wants non-null LePE weights; nothing is dereferenced
+    a = geom.args(B, [z] * len(geom.branches), [z] * len(geom.branches))
+    plan = _lib.StripePlan()
+    check(lib().csu_stripe_attn_plan(ctypes.byref(a), dtype_code_of(dtype), ctypes.byref(plan)), "stripe_attn_plan")
+    return plan
 
 
 class AttnDrop:

@@ -70,7 +70,11 @@ typedef struct {
     int32_t head_dim;        /* must be 32 (embed_dim is hard-wired to 64: SURVEY §0.5) */
     int32_t nbranch;         /* 1 (last stage, idx -1) or 2 (idx 0 and idx 1) */
     float scale;             /* qk_scale or head_dim**-0.5 (cswin:231) */
-    int32_t _pad;
+    int32_t split;           /* workgroups per window-head of the whole-window bf16 kernels: 0 = the
+                              * heuristic, 1 .. ceil(roundup32(N) / 128) forces that factor (tests,
+                              * tuning).  The range is checked in every call and dtype (anything else is
+                              * CSU_E_ARG, so the field must be initialised: it was padding before); the
+                              * value is used only where a whole-window bf16 kernel runs */
     csu_stripe_branch br[2];
     /* attention dropout on the softmax probabilities (attn_drop, cswin:290), p = 0: none.  rng =
      * device [seed, counter] snapshot of the step (uint64 x 2), the same for forward and backward;
@@ -115,6 +119,55 @@ typedef struct {
     int32_t nblk, channels, nbranch, _pad;
 } csu_lepe_reduce_item;
 int csu_stripe_lepe_reduce_batch(const csu_lepe_reduce_item* items, int count, void* stream);
+
+/* The launch plan of a stripe-attention call: which kernel instance csu_stripe_attn_fwd /
+ * csu_stripe_attn_bwd(_ex) / csu_stripe_lepe_wgrad run for (args, dtype) and how each divides the
+ * window.  Host only, no HIP call: it is the function the launch layer itself takes every decision
+ * from, so the report cannot differ from what is launched. */
+enum csu_stripe_kernel {
+    CSU_STRIPE_STREAMED = 0,      /* stripe_fwd / stripe_bwd_dq + _dkdv: one workgroup per 128-row block */
+    CSU_STRIPE_WINDOW = 1,        /* stripe_fwd_w / stripe_bwd_dq_w + _dkdv_w: whole window in LDS, split */
+    CSU_STRIPE_FUSED_BWD = 2      /* stripe_bwd_fused_w: one-pass backward, one workgroup per window-head */
+};
+enum csu_lepe_kernel {
+    CSU_LEPE_IN_FUSED_BWD = 0,    /* pass 1 (block partials) formed inside stripe_bwd_fused_w */
+    CSU_LEPE_TILES = 1,           /* lepe_wgrad_tiles */
+    CSU_LEPE_PARTIAL = 2          /* lepe_wgrad_partial */
+};
+enum csu_stripe_plan_flags {
+    CSU_PLAN_RAGGED_PASS = 1,     /* a workgroup's last of several passes has idle waves */
+    CSU_PLAN_EMPTY_PARTNER = 2    /* a split partner owns no rows (its first row is at or past the padded
+                                   * window's end): odd splits only, e.g. sp 7 for windows of 897..960 tokens */
+};
+typedef struct {
+    int32_t kernel;               /* csu_stripe_kernel */
+    int32_t wm;                   /* LDS image rows of the instance (WINDOW, FUSED_BWD), else 0 */
+    int32_t sp;                   /* split factor chosen (args.split or the heuristic); 1 where no split kernel runs */
+    int32_t split;                /* workgroups per window-head as launched (sp, or sp / 2 with 8 waves;
+                                   * STREAMED: the 128-row blocks of the window) */
+    int32_t waves;                /* waves per workgroup */
+    int32_t rows;                 /* rows a workgroup owns (STREAMED: 128; FUSED_BWD: wm) */
+    int32_t passes;               /* most passes of 32 * waves rows a wave makes over its workgroup's rows
+                                   * (FUSED_BWD: key tiles per wave) */
+    int32_t flags;                /* csu_stripe_plan_flags */
+} csu_stripe_kernel_plan;
+typedef struct {
+    csu_stripe_kernel_plan fwd, bwd;
+    int32_t lepe_kernel;          /* csu_lepe_kernel: where pass 1 of csu_stripe_attn_bwd's LePE weight gradient runs */
+    int32_t lepe_nblk;            /* block partials it leaves (csu_stripe_lepe_nblk) */
+    /* the stand-alone pass 1 (csu_stripe_lepe_wgrad; the backward's too unless IN_FUSED_BWD) */
+    int32_t wgrad_kernel;         /* CSU_LEPE_TILES or CSU_LEPE_PARTIAL */
+    int32_t wgrad_nblk;           /* its block partials per branch */
+    int32_t tile_rows;            /* TILES: image rows per tile, rows per block, tiles per block (PARTIAL: 0) */
+    int32_t rows_blk;
+    int32_t tiles_blk;
+    int32_t wgrad_flags;          /* TILES: 1 = an image's last block has fewer rows than rows_blk,
+                                   *        2 = a block's last tile reaches past the block's rows */
+    int32_t ws_blocks;            /* partial blocks per branch the workspace is sized for (either dtype) */
+    int32_t _pad;
+} csu_stripe_plan;
+/* Runs the same validation as the launches; 0 or a csu_status. */
+int csu_stripe_attn_plan(const csu_stripe_args* a, int dtype, csu_stripe_plan* out);
 
 /* ---------------------------------------------------------------------------------------
  * LayerNorm over the last dim C of (rows, C) (nn.LayerNorm: norm1/norm2 cswin:315/347,

@@ -44,7 +44,9 @@ def test_struct_layout_matches_header(tmp_path):
     import subprocess
     from csu import _lib
     checks = {"csu_stripe_branch": (_lib.StripeBranch, ["H_sp", "ch_off", "lepe_w", "lepe_db"]),
-              "csu_stripe_args": (_lib.StripeArgs, ["scale", "br", "drop_rng", "drop_site", "drop_p"]),
+              "csu_stripe_args": (_lib.StripeArgs, ["scale", "split", "br", "drop_rng", "drop_site", "drop_p"]),
+              "csu_stripe_plan": (_lib.StripePlan, ["fwd", "bwd", "lepe_kernel", "wgrad_kernel", "tile_rows", "wgrad_flags", "ws_blocks"]),
+              "csu_stripe_kernel_plan": (_lib.StripeKernelPlan, ["kernel", "sp", "split", "passes", "flags"]),
               "csu_gemm_desc": (_lib.GemmDesc, ["M", "a", "b_trans", "bias", "out", "ldc", "cfg"]),
               "csu_mlp_dropout": (_lib.MlpDropout, ["rng", "site_out", "p", "row_scale", "rows_per_sample"]),
               "csu_conv_geom": (_lib.ConvGeom, ["B", "KH", "pad"]),
