@@ -1411,30 +1411,6 @@ int fwd_launch(long M, const void* x, const void* w1, const float* b1, const voi
     return check_launch(ln ? "mlp_fwd_ln" : "mlp_fwd");
 }
 
-template <int C>
-int bwd_launch(long M, const void* x, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
-               void* dx, const MlpDrop* d, long rpi, hipStream_t st) {
-    const dim3 grid((unsigned)((M + BM - 1) / BM));
-    const auto X = (const bf16*)x, dY = (const bf16*)dy, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
-    const auto dH = (bf16*)dh, G = (bf16*)g, dX = (bf16*)dx;
-    const MlpDrop dd = d ? *d : MlpDrop{};
-    if constexpr (C == 256) {   // two waves per SIMD; only dropout launches keep the 4-wave kernel
-        if (!d) mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi, MlpLnb{});
-        else mlp_bwd_kernel<C, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
-    } else {
-        with_flag(d != nullptr, [&](auto df) {
-            constexpr bool D = decltype(df)::value;
-            if constexpr (C == 64)   // persistent, weights resident
-                mlp_bwd64<D, false><<<dim3((unsigned)persist_grid(M)), 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX,
-                                                                                        nullptr, nullptr, dd);
-            else
-                mlp_bwd_kernel<C, D><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
-        });
-    }
-    return check_launch("mlp_bwd");
-}
-
-
 
 // ================================================================================================
 // fp8-e4m3 fused Mlp (BASELINE config 5, "fp8 MFMA weights"): v_mfma_scale_f32_32x32x64_f8f6f4 with
@@ -1951,171 +1927,16 @@ int fp8_bwd_launch(long M, const void* x, const void* dy, const void* w1, const 
 
 
 // ================================================================================================
-// Deep-ring forward (bf16): the per-panel kernel above keeps ONE 64-KB weight chunk in flight, and
-// its step time is the DMA time of that chunk (~25 GB/s per CU: 2.5 us per chunk at C = 256, 16
-// chunks); the LDS-DMA path delivers several times that with more bytes in flight
-// (MI355X_MICROARCH.md, ring-gemm).  Here chunks are 32 hidden features (W1 [32][C] + W2 [C][32]
-// = 128 C bytes) in an RS-stage ring with RS - 1 chunks in flight, and the waves split the panel by
-// TOKENS: wave w owns tokens 16 w .. 16 w + 15 with every hidden feature of the chunk and every
-// output feature (v_mfma_f32_16x16x32_bf16), so nothing is exchanged between waves.
-//   GEMM1  h[32 hid][16 tok] = W1c x^T   (two 16-row tiles, k = C in steps of 32)
-//   GELU   lane (tok, kg) holds hidden 4 kg + i of both tiles -> the 8 k-values of GEMM2's B
-//          operand in the permuted order (4 kg + i, 16 + 4 kg + i); W2 is read in the same order
-//   GEMM2  y[C][16 tok] += W2c g        (C / 16 tiles, one k-step of 32)
+// The C = 128 backward (bf16): the deep weight ring.  The per-panel kernel above keeps ONE 64-KB weight
+// chunk in flight, and its step time is the DMA time of that chunk; the LDS-DMA path delivers several
+// times that with more bytes in flight (MI355X_MICROARCH.md, ring-gemm).  Here chunks are 32 hidden
+// features (W1 [32][C] + W2 [C][32] = 128 C bytes) in an RS-stage ring with RS - 1 chunks in flight, and
+// the waves split the panel by TOKENS: wave w owns tokens 16 w .. 16 w + 15 with every hidden feature of
+// the chunk and every output feature (v_mfma_f32_16x16x32_bf16), so nothing is exchanged between waves.
 // Every step issues exactly one chunk's DMA (past the last chunk it re-fetches the last one into the
-// free stage), so the wait for chunk j is a fixed count.
-template <int C, int RS, bool DROP>
-__global__ __launch_bounds__(MT) void mlp_fwd_deep(long M, const bf16* __restrict__ X, const bf16* __restrict__ W1,
-                                                   const float* __restrict__ b1, const bf16* __restrict__ W2,
-                                                   const float* __restrict__ b2, const float* __restrict__ res,
-                                                   float* __restrict__ out, MlpDrop dd, long rpi) {
-    constexpr int HD = 32;                 // hidden features per chunk
-    constexpr int NCH = 4 * C / HD;
-    constexpr int KS = C / 32;             // GEMM1 k-steps
-    constexpr int OT = C / 16;             // output tiles
-    constexpr int IMG1 = HD * C;           // bf16 of a W1 chunk image [32][C]
-    constexpr int IMG2 = C * HD;           // and of a W2 chunk image [C][32]
-    constexpr int STAGE = IMG1 + IMG2;
-    using D1 = Dma<HD, 2 * C>;
-    using D2 = Dma<C, 2 * HD>;
-    constexpr int ND = D1::NW + D2::NW;    // DMA instructions per wave per chunk
-    __shared__ __attribute__((aligned(1024))) bf16 ring[RS * STAGE];
-    __shared__ __attribute__((aligned(16))) float b1s[4 * C];
-
-    const long m0 = (long)blockIdx.x * BM;
-    const long rows = M - m0;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int l16 = lane & 15, kg = lane >> 4;
-    const int tok = 16 * wave + l16;
-    const bool ok = tok < rows;
-    const int j0 = kRot && rpi > 0 && rpi % BM == 0 ? (int)(((m0 % rpi) / BM) & (NCH - 1)) : 0;   // see mlp_fwd_kernel
-    auto chk = [&](int j) { return (j + j0) & (NCH - 1); };
-    for (int i = threadIdx.x; i < 4 * C; i += MT) b1s[i] = b1[i];
-    // x as GEMM1 B fragments: lane (tok, kg) of k-step s = x[tok][32 s + 8 kg .. + 7]
-    bf16x8 xf[KS];
-    {
-        const auto rs = buf_rsrc(X + m0 * C, rows * C * 2);
-#pragma unroll
-        for (int s2 = 0; s2 < KS; ++s2) {
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (unsigned)(tok * C + 32 * s2 + 8 * kg) * 2 : kOOB, 0, 0);
-            __builtin_memcpy(&xf[s2], &v, 16);
-        }
-    }
-    D1 d1;
-    D2 d2;
-    d1.init(C, wave, lane);
-    d2.init(4 * C, wave, lane);
-    const i32x4 rs_w1 = rsrc4(W1, 4L * C * C * 2);
-    const i32x4 rs_w2 = rsrc4(W2, 4L * C * C * 2);
-    auto issue = [&](int j) {   // chunk min(j, NCH - 1) into stage j % RS
-        const int jc = chk(j < NCH ? j : NCH - 1);
-        bf16* st = ring + (j % RS) * STAGE;
-        dma<D1::NW>(rs_w1, d1.v, (unsigned)jc * HD * C * 2, st, wave);
-        dma<D2::NW>(rs_w2, d2.v, (unsigned)jc * HD * 2, st + IMG1, wave);
-    };
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < RS - 1; ++j) issue(j);
-    f32x4 acc[OT];
-#pragma unroll
-    for (int i = 0; i < OT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const long mg = m0 + tok;
-    DropoutRng Rh;
-    if constexpr (DROP) Rh = load_rng(dd.rng, dd.site_h, dd.p);
-    __syncthreads();   // b1s
-    for (int j = 0; j < NCH; ++j) {
-        vmwait<(RS - 2) * ND>();          // chunk j landed (younger: chunks j + 1 .. j + RS - 2)
-        lds_sync();                       // ... for every wave; stage (j - 1) % RS is free
-        issue(j + RS - 1);
-        const bf16* w1c = ring + (j % RS) * STAGE;
-        const bf16* w2c = w1c + IMG1;
-        const int jc = chk(j);
-        f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s2 = 0; s2 < KS; ++s2) {
-            const bf16x8 a0 = frag(w1c, moff<2 * C>(l16, 32 * s2 + 8 * kg));
-            const bf16x8 a1 = frag(w1c, moff<2 * C>(16 + l16, 32 * s2 + 8 * kg));
-            h0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, xf[s2], h0, 0, 0, 0);
-            h1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, xf[s2], h1, 0, 0, 0);
-        }
-        // GELU: hidden jc * 32 + 4 kg + i (tile 0) and + 16 (tile 1)
-        const f32x4 bv0 = *reinterpret_cast<const f32x4*>(b1s + jc * HD + 4 * kg);
-        const f32x4 bv1 = *reinterpret_cast<const f32x4*>(b1s + jc * HD + 16 + 4 * kg);
-        float gv[8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            gv[i] = gelu_fast(h0[i] + bv0[i]);
-            gv[4 + i] = gelu_fast(h1[i] + bv1[i]);
-        }
-        if constexpr (DROP) {
-            if (dd.p > 0.f) {
-                const uint64_t e0 = (uint64_t)mg * 4 * C + jc * HD + 4 * kg;   // 4-aligned; its 8-group
-                const unsigned m0b = keep8(Rh, e0 >> 3) >> (e0 & 7);
-                const unsigned m1b = keep8(Rh, (e0 + 16) >> 3) >> ((e0 + 16) & 7);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    gv[i] = ((m0b >> i) & 1u) ? gv[i] * Rh.scale : 0.f;
-                    gv[4 + i] = ((m1b >> i) & 1u) ? gv[4 + i] * Rh.scale : 0.f;
-                }
-            }
-        }
-        bf16x8 gb;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) gb[i] = (bf16)gv[i];
-#pragma unroll
-        for (int ot = 0; ot < OT; ++ot) {   // A: W2[out][hidden 4 kg + i, 16 + 4 kg + i] (the same k order)
-            const bf16x4 lo = *reinterpret_cast<const bf16x4*>(w2c + moff<2 * HD>(16 * ot + l16, 4 * kg));
-            const bf16x4 hi = *reinterpret_cast<const bf16x4*>(w2c + moff<2 * HD>(16 * ot + l16, 16 + 4 * kg));
-            const bf16x8 a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, gb, acc[ot], 0, 0, 0);
-        }
-    }
-    // epilogue: acc[ot][i] = y[tok][16 ot + 4 kg + i]
-    const auto rs_res = buf_rsrc(res + m0 * C, rows * C * 4);
-    const auto rs_out = buf_rsrc(out + m0 * C, rows * C * 4);
-    float sdp = 1.f;
-    DropoutRng R;
-    if constexpr (DROP) {
-        R = load_rng(dd.rng, dd.site_o, dd.p);
-        if (dd.row_scale) sdp = dd.row_scale[mg / dd.rps];
-    }
-#pragma unroll
-    for (int ot = 0; ot < OT; ++ot) {
-        const int f = 16 * ot + 4 * kg;
-        const unsigned off = ok ? (unsigned)(tok * C + f) * 4 : kOOB;
-        float rv[4], bv[4], v[4];
-        buf_ld4(rs_res, off, rv);
-        load4(b2 + f, bv);
-        unsigned km = 0xfu;
-        if constexpr (DROP) if (dd.p > 0.f) {
-            const uint64_t e = (uint64_t)mg * C + f;
-            km = keep8(R, e >> 3) >> (e & 7);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float z = acc[ot][e] + bv[e];
-            if constexpr (DROP) z *= ((km >> e) & 1u) ? sdp * R.scale : 0.f;
-            v[e] = z + rv[e];
-        }
-        buf_st4(rs_out, off, v);
-    }
-    vmwait<0>();   // the re-fetch DMAs drained before the workgroup's LDS is released
-}
-
-template <int C, int RS>
-int fwd_deep_launch(long M, const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const float* res,
-                    float* out, const MlpDrop* d, long rpi, hipStream_t st) {
-    const dim3 grid((unsigned)((M + BM - 1) / BM));
-    const MlpDrop dd = d ? *d : MlpDrop{};
-    with_flag(d != nullptr, [&](auto df) {
-        mlp_fwd_deep<C, RS, decltype(df)::value><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)w1, b1, (const bf16*)w2, b2,
-                                                                      res, out, dd, rpi);
-    });
-    return check_launch("mlp_fwd (deep)");
-}
-
-
+// free stage), so the wait for chunk j is a fixed count.  Only C = 128 with RS = kBwdRing128 is built:
+// 61.0 vs 75.2 us for the per-panel kernel at 65536 tokens (profiles/r06b_mlp8_probe.txt); C = 64 / 256
+// and the same ring for the forward measured equal or slower (DESIGN, "Measured and NOT kept (round 4)").
 
 // 16x16x32 operand fragments transposed out of a moff<RB> image whose ROWS are k and COLUMNS are i
 // (ds_read_b64_tr_b16: lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3 and receives
@@ -2125,7 +1946,7 @@ __device__ __forceinline__ bf16x8 tr16n(const bf16* img, int c0, int k0, int lan
     const int kg = lane >> 4, l = lane & 15, q = l >> 2, p = l & 3;
     return cat8(tr4(img + moff<RB>(k0 + 8 * kg + q, c0 + 4 * p)), tr4(img + moff<RB>(k0 + 8 * kg + 4 + q, c0 + 4 * p)));
 }
-// ... or k = k0 + 4 kg + 0..3, k0 + 16 + 4 kg + 0..3 (the deep-ring kernels' permuted hidden order)
+// ... or k = k0 + 4 kg + 0..3, k0 + 16 + 4 kg + 0..3 (the deep-ring kernel's permuted hidden order)
 template <int RB>
 __device__ __forceinline__ bf16x8 tr16p(const bf16* img, int c0, int k0, int lane) {
     const int kg = lane >> 4, l = lane & 15, q = l >> 2, p = l & 3;
@@ -2141,8 +1962,8 @@ template <int N> __device__ __forceinline__ void vmwait_le(int c) {   // s_waitc
     }
 }
 
-// Deep-ring backward (bf16): the forward's chunking and token split.  Per chunk j (32 hidden):
-//   GEMM1  h  = W1c x^T                      (A: W1 image rows, as the forward)
+// Per chunk j (32 hidden), lane (tok, kg) of a wave:
+//   GEMM1  h  = W1c x^T                      (A: W1 image rows; two 16-row tiles, k = C in steps of 32)
 //   GEMM3  dg = W2c^T dY^T                   (A: transposed reads of the W2 image [C][32], k = C natural)
 //   dh = dg * gelu'(h) (* hidden mask), g = gelu(h) (* mask): stored (bf16) for the weight gradients
 //   GEMM4  dx += W1c^T dh                    (A: transposed reads of the W1 image, k = the chunk's hidden
@@ -2310,35 +2131,60 @@ __global__ __launch_bounds__(MT) void mlp_bwd_deep(long M, const bf16* __restric
     vmwait<0>();
 }
 
-// ring stages of the deep-ring kernels (csu_mlp_*_ex cfg 1, or cfg 2 = DEEPER)
-template <int C, bool DEEPER> constexpr int kDeepRs = DEEPER ? (C == 64 ? 8 : C == 128 ? 6 : 3) : (C == 64 ? 6 : 4);
+constexpr int kBwdRing128 = 4;   // ring stages of mlp_bwd_deep at C = 128: 3 chunks of 32 hidden in flight
 
-template <int C, int RS>
-int bwd_deep_launch(long M, const void* x, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
-                    void* dx, const MlpDrop* d, long rpi, hipStream_t st) {
-    const dim3 grid((unsigned)((M + BM - 1) / BM));
-    const MlpDrop dd = d ? *d : MlpDrop{};
-    with_flag(d != nullptr, [&](auto df) {
-        mlp_bwd_deep<C, RS, decltype(df)::value><<<grid, MT, 0, st>>>(M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1,
-                                                                      (const bf16*)w2, (bf16*)dh, (bf16*)g, (bf16*)dx, dd, rpi,
-                                                                      MlpLnb{});
-    });
-    return check_launch("mlp_bwd (deep)");
-}
+// What a backward launch does besides csu_mlp_bwd_dp's arguments; the entry points check what their width supports
+struct BwdMode {
+    const MlpLnb* ln = nullptr;   // norm2's backward in the row phase (C = 128 / 256, no dropout, M % 64 == 0): dx is not written
+    float* slab1 = nullptr;       // the weight-gradient partials (C = 64, wgrad_grid(M) workgroups): dh and g are not written
+    float* slab2 = nullptr;
+    bool per_panel = false;       // C = 128: csu_mlp_bwd_per_panel
+};
 
-// The Mlp backward with norm2's LayerNorm backward in its row phase (LNB): C = 128 the deep ring, C = 256 the
-// 8-wave kernel -- the kernels csu_mlp_bwd_dp runs at those widths
+// The backward launch layer: every backward entry point launches through here, and this table is the whole choice
+// (D = dropout, d != nullptr):
+//   C     no dropout                        dropout                      norm2 backward (m.ln)
+//   64    mlp_bwd64<-, WGRAD>               mlp_bwd64<D, WGRAD>          --                              WGRAD = m.slab1 given
+//   128   mlp_bwd_deep<128, 4, ->           mlp_bwd_deep<128, 4, D>      mlp_bwd_deep<128, 4, -, LNB>
+//         mlp_bwd_kernel<128, ->            mlp_bwd_kernel<128, D>       --                              m.per_panel
+//   256   mlp_bwd8_kernel<256>              mlp_bwd_kernel<256, D>       mlp_bwd8_kernel<256, LNB>
+// C = 64 is persistent with the weights resident; C = 256 runs two waves per SIMD and only dropout launches keep
+// the 4-wave per-panel kernel.
 template <int C>
-int bwd_ln_launch(long M, const void* h, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
-                  long rpi, const MlpLnb& ln, hipStream_t st) {
-    const dim3 grid((unsigned)(M / BM));
-    const auto X = (const bf16*)h, dY = (const bf16*)dy, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
-    if constexpr (C == 256)
-        mlp_bwd8_kernel<C, true><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, (bf16*)dh, (bf16*)g, nullptr, rpi, ln);
-    else
-        mlp_bwd_deep<C, kDeepRs<C, false>, false, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, (bf16*)dh, (bf16*)g, nullptr,
-                                                                            MlpDrop{}, rpi, ln);
-    return check_launch("mlp_bwd_ln");
+int bwd_launch(long M, const void* x, const void* dy, const void* w1, const float* b1, const void* w2, void* dh, void* g,
+               void* dx, const MlpDrop* d, long rpi, hipStream_t st, const BwdMode& m = BwdMode{}) {
+    const dim3 grid((unsigned)((M + BM - 1) / BM));
+    const auto X = (const bf16*)x, dY = (const bf16*)dy, W1 = (const bf16*)w1, W2 = (const bf16*)w2;
+    const auto dH = (bf16*)dh, G = (bf16*)g, dX = (bf16*)dx;
+    const MlpDrop dd = d ? *d : MlpDrop{};
+    const char* what = "mlp_bwd";
+    if constexpr (C == 64) {
+        with_flag(d != nullptr, [&](auto df) {
+            with_flag(m.slab1 != nullptr, [&](auto wf) {
+                constexpr bool WGRAD = decltype(wf)::value;
+                const dim3 pgrid((unsigned)(WGRAD ? wgrad_grid(M) : persist_grid(M)));
+                mlp_bwd64<decltype(df)::value, WGRAD><<<pgrid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, m.slab1, m.slab2,
+                                                                               dd);
+            });
+        });
+        if (m.slab1) what = "mlp_bwd_wgrad";
+    } else if (m.ln) {
+        if constexpr (C == 256) mlp_bwd8_kernel<C, true><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi, *m.ln);
+        else mlp_bwd_deep<C, kBwdRing128, false, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi, *m.ln);
+        what = "mlp_bwd_ln";
+    } else if constexpr (C == 256) {
+        if (!d) mlp_bwd8_kernel<C><<<grid, 2 * MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, rpi, MlpLnb{});
+        else mlp_bwd_kernel<C, true><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
+    } else {
+        static_assert(C == 128, "bwd_launch: C is 64, 128 or 256");
+        with_flag(d != nullptr, [&](auto df) {
+            constexpr bool D = decltype(df)::value;
+            if (m.per_panel) mlp_bwd_kernel<C, D><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi);
+            else mlp_bwd_deep<C, kBwdRing128, D><<<grid, MT, 0, st>>>(M, X, dY, W1, b1, W2, dH, G, dX, dd, rpi, MlpLnb{});
+        });
+        if (!m.per_panel) what = "mlp_bwd (deep)";
+    }
+    return check_launch(what);
 }
 
 }  // namespace
@@ -2426,12 +2272,22 @@ extern "C" int csu_mlp_bwd_dp(long M, int C, const void* x, const void* dy, cons
     MlpArgs a;
     if (const int e = mlp_args("mlp_bwd", {x, dy, w1, b1, w2, dh, g, dx}, M, C, d, stream, a)) return e;
     return dispatch_c("mlp_bwd", C, CSU_E_ARG, [&](auto c) {
-        constexpr int CC = decltype(c)::value;
-        // C = 128: the deep ring (4 chunks of 32 hidden in flight) measured 61.0 vs 75.2 us at 65536
-        // tokens (profiles/r06b_mlp8_probe.txt); C = 64 / 256: the persistent / per-panel kernels (equal or faster)
-        if constexpr (CC == 128) return bwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
-        else return bwd_launch<CC>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
+        return bwd_launch<decltype(c)::value>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
     });
+}
+
+// csu_mlp_bwd_dp at C = 128 on the per-panel kernel mlp_bwd_kernel<128, DROP>, which no product path launches (the
+// product runs the deep ring there).  It exists for the parity tests of the two kernels, and because the code the
+// compiler generates for the C = 128 forward mlp_fwd_kernel<128, *, *> depends on this kernel being instantiated in
+// the same file (profiles/mlp_deep_retire_ab.txt): removing it is a change that has to re-measure the forward.
+extern "C" int csu_mlp_bwd_per_panel(long M, int C, const void* x, const void* dy, const void* w1, const float* b1,
+                                     const void* w2, void* dh, void* g, void* dx, const csu_mlp_dropout* d, void* stream) {
+    MlpArgs a;
+    if (const int e = mlp_args("mlp_bwd_per_panel", {x, dy, w1, b1, w2, dh, g, dx}, M, C, d, stream, a)) return e;
+    if (C != 128) return fail(CSU_E_ARG, "mlp_bwd_per_panel: C must be 128");
+    BwdMode m;
+    m.per_panel = true;
+    return bwd_launch<128>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st, m);
 }
 
 extern "C" int csu_mlp_bwd_ln_supported(long M, int C) { return (C == 128 || C == 256) && M >= BM && M % BM == 0; }
@@ -2445,8 +2301,10 @@ extern "C" int csu_mlp_bwd_ln(long M, int C, const void* h, const void* dy, cons
         return e;
     if (!csu_mlp_bwd_ln_supported(M, C)) return fail(CSU_E_ARG, "mlp_bwd_ln: C must be 128 or 256 and M a multiple of 64");
     const MlpLnb ln{x, gamma, mean, rstd, dres, dx, (bf16*)dx_bf16, part};
-    if (C == 128) return bwd_ln_launch<128>(M, h, dy, w1, b1, w2, dh, g, rows_per_image, ln, a.st);
-    return bwd_ln_launch<256>(M, h, dy, w1, b1, w2, dh, g, rows_per_image, ln, a.st);
+    BwdMode m;
+    m.ln = &ln;
+    if (C == 128) return bwd_launch<128>(M, h, dy, w1, b1, w2, dh, g, nullptr, nullptr, rows_per_image, a.st, m);
+    return bwd_launch<256>(M, h, dy, w1, b1, w2, dh, g, nullptr, nullptr, rows_per_image, a.st, m);
 }
 
 extern "C" int csu_mlp_bwd(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
@@ -2476,14 +2334,12 @@ extern "C" int csu_mlp_bwd_wgrad(long M, int C, const void* x, const void* dy, c
         return e;
     if (!csu_mlp_bwd_wgrad_supported(C)) return fail(CSU_E_ARG, "mlp_bwd_wgrad: C must be 64");
     const int grid = wgrad_grid(M);
-    with_flag(a.dp != nullptr, [&](auto df) {
-        mlp_bwd64<decltype(df)::value, true><<<dim3((unsigned)grid), 2 * MT, 0, a.st>>>(
-            M, (const bf16*)x, (const bf16*)dy, (const bf16*)w1, b1, (const bf16*)w2, nullptr, nullptr, (bf16*)dx, slab1, slab2,
-            a.dp ? a.md : MlpDrop{});
-    });
     *item1 = csu_wslab_item{slab1, dw1_db1, 4 * C, C, 32, 32, grid, 0};
     *item2 = csu_wslab_item{slab2, dw2_db2, C, 4 * C, 32, 32, grid, 0};
-    return check_launch("mlp_bwd_wgrad");
+    BwdMode m;
+    m.slab1 = slab1;
+    m.slab2 = slab2;
+    return bwd_launch<64>(M, x, dy, w1, b1, w2, nullptr, nullptr, dx, a.dp, a.rpi, a.st, m);
 }
 
 extern "C" int csu_mlp_fp8_supported(int C) { return C == 64 || C == 128 || C == 256; }
@@ -2521,34 +2377,5 @@ extern "C" int csu_mlp_fp8_bwd(long M, int C, const void* x, const void* dy, con
     if (const int e = mlp_args("mlp_fp8_bwd", {x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx}, M, C, d, stream, a)) return e;
     return dispatch_c("mlp_fp8_bwd", C, CSU_E_UNSUPPORTED, [&](auto c) {
         return fp8_bwd_launch<decltype(c)::value>(M, x, dy, w1q, sw1, b1, w2t, sw2, w1tp, dh, g, dx, a.dp, a.rpi, a.st);
-    });
-}
-
-// explicit forward variant (tests, tools/mlp8_probe.py): cfg 0 = the per-panel kernel, 1 = the deep ring, 2 = deeper rings
-extern "C" int csu_mlp_fwd_ex(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
-                              const float* res, float* out, const csu_mlp_dropout* d, int cfg, void* stream) {
-    if (cfg == 0) return csu_mlp_fwd_dp(M, C, x, w1, b1, w2, b2, res, out, d, stream);
-    if (cfg != 1 && cfg != 2) return fail(CSU_E_ARG, "mlp_fwd_ex: cfg 0, 1 or 2");
-    MlpArgs a;
-    if (const int e = mlp_args("mlp_fwd", {x, w1, b1, w2, b2, res, out}, M, C, d, stream, a)) return e;
-    return dispatch_c("mlp_fwd", C, CSU_E_ARG, [&](auto c) {
-        constexpr int CC = decltype(c)::value;
-        return cfg == 2 ? fwd_deep_launch<CC, kDeepRs<CC, true>>(M, x, w1, b1, w2, b2, res, out, a.dp, a.rpi, a.st)
-                        : fwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, w1, b1, w2, b2, res, out, a.dp, a.rpi, a.st);
-    });
-}
-
-// explicit backward variant: cfg 0 = the per-panel / persistent kernels, 1 / 2 = the deep ring (csu_mlp_bwd_dp:
-// cfg 1 at C = 128, cfg 0 otherwise)
-extern "C" int csu_mlp_bwd_ex(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
-                              void* dh, void* g, void* dx, const csu_mlp_dropout* d, int cfg, void* stream) {
-    if (cfg != 0 && cfg != 1 && cfg != 2) return fail(CSU_E_ARG, "mlp_bwd_ex: cfg 0, 1 or 2");
-    MlpArgs a;
-    if (const int e = mlp_args("mlp_bwd", {x, dy, w1, b1, w2, dh, g, dx}, M, C, d, stream, a)) return e;
-    return dispatch_c("mlp_bwd", C, CSU_E_ARG, [&](auto c) {
-        constexpr int CC = decltype(c)::value;
-        if (cfg == 0) return bwd_launch<CC>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
-        return cfg == 2 ? bwd_deep_launch<CC, kDeepRs<CC, true>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st)
-                        : bwd_deep_launch<CC, kDeepRs<CC, false>>(M, x, dy, w1, b1, w2, dh, g, dx, a.dp, a.rpi, a.st);
     });
 }

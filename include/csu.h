@@ -719,14 +719,11 @@ int csu_mlp_bwd_wgrad(long M, int C, const void* x, const void* dy, const void* 
 int csu_mlp_fwd_ln(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                    const float* res, float* out, const csu_mlp_dropout* d, const float* ln_gamma, const float* ln_beta,
                    float ln_eps, void* ln_out, float* ln_mean, float* ln_rstd, void* stream);
-/* the forward with an explicit kernel: cfg 0 = the per-panel kernel (csu_mlp_fwd_dp), 1 / 2 = the deep
- * weight ring (32-hidden chunks, several in flight, waves split by tokens; 2: another ring depth) */
-int csu_mlp_fwd_ex(long M, int C, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
-                   const float* res, float* out, const csu_mlp_dropout* d, int cfg, void* stream);
-/* the backward with an explicit kernel: cfg 0 = the per-panel kernels, 1 / 2 = the deep ring (csu_mlp_bwd_dp
- * runs cfg 1 at C = 128 and cfg 0 otherwise) */
-int csu_mlp_bwd_ex(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
-                   void* dh, void* g, void* dx, const csu_mlp_dropout* d, int cfg, void* stream);
+/* csu_mlp_bwd_dp at C = 128 (any other C: CSU_E_ARG) on the per-panel kernel instead of the deep weight ring
+ * that csu_mlp_bwd_dp runs there.  No product path calls it: it exists for the parity tests of the two kernels,
+ * and because the compiled C = 128 forward depends on that kernel being built (DESIGN, "Kept, default-off"). */
+int csu_mlp_bwd_per_panel(long M, int C, const void* x, const void* dy, const void* w1, const float* b1, const void* w2,
+                          void* dh, void* g, void* dx, const csu_mlp_dropout* d, void* stream);
 /* fp8-e4m3 fused Mlp forward (BASELINE config 5, "fp8 MFMA weights"; same math and dropout as
  * csu_mlp_fwd_dp) on v_mfma_scale_f32_32x32x64_f8f6f4 with MX block scales:
  *   h   = x_q W1^T + b1, x_q = x quantised per (token, 32 consecutive channels): scale 2^e, e the

@@ -477,10 +477,12 @@ def _check_mlp(c, got, name):
               c["tail"][k] if ref.dim() == 2 else c["tail"][k].view(1, -1), f"{name} {k}")
 
 
-@pytest.mark.parametrize("C,M", E.MLP_CASES)
-@pytest.mark.parametrize("variant", ["default", "cfg1", "cfg2", "dp"])
+_MLP_FUSED = [(v, C, M) for v in ("default", "dp", "per_panel") for C, M in E.MLP_CASES if v != "per_panel" or C == 128]
+
+
+@pytest.mark.parametrize("variant,C,M", _MLP_FUSED, ids=[f"{v}-{C}-{M}" for v, C, M in _MLP_FUSED])
 def test_mlp_fused(C, M, variant):
-    """csu_mlp_fwd / csu_mlp_bwd, the deep-ring csu_mlp_fwd_ex / csu_mlp_bwd_ex (cfg 1, 2), and csu_mlp_bwd_dp --
+    """csu_mlp_fwd / csu_mlp_bwd, csu_mlp_bwd_dp, and at C = 128 the per-panel backward csu_mlp_bwd_per_panel --
     at C = 64 also csu_mlp_bwd_wgrad, which forms dW1 / db1 / dW2 / db2 inside the kernel: y, g, dh, dx (and the
     four weight gradients) against the ReLU network.  The activations are even (exact_inputs.mlp_case), so no hidden
     value is -8 and every tail is exactly 0: with activations in {-2..2} the bf16 MFMA dot product, given the ~1e-14
@@ -501,17 +503,15 @@ def test_mlp_fused(C, M, variant):
     if variant == "default":
         ok(L.csu_mlp_fwd(M, C, ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(res), ptr(y), st), "mlp_fwd")
         ok(L.csu_mlp_bwd(M, C, ptr(x), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(dh), ptr(g), ptr(dx), st), "mlp_bwd")
-    elif variant in ("cfg1", "cfg2"):
-        cfg, md = int(variant[-1]), _no_drop(M)
-        ok(L.csu_mlp_fwd_ex(M, C, ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(res), ptr(y), ctypes.byref(md), cfg, st),
-           "mlp_fwd_ex")
-        ok(L.csu_mlp_bwd_ex(M, C, ptr(x), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(dh), ptr(g), ptr(dx), ctypes.byref(md), cfg,
-                            st), "mlp_bwd_ex")
+    elif variant == "per_panel":
+        md = _no_drop(M)
+        ok(L.csu_mlp_bwd_per_panel(M, C, ptr(x), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(dh), ptr(g), ptr(dx), ctypes.byref(md),
+                                   st), "mlp_bwd_per_panel")
     else:
         ok(L.csu_mlp_bwd_dp(M, C, ptr(x), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(dh), ptr(g), ptr(dx), None, st), "mlp_bwd_dp")
     torch.cuda.synchronize()
     got = {"g": g, "dh": dh, "dx": dx}
-    if variant != "dp":
+    if variant == "default":
         got["y"] = y
     _check_mlp(c, got, name)
     if variant == "dp" and C == 64:

@@ -1038,14 +1038,14 @@ def _mlp_raw(C, M, seed):
     return x, w1, w2, b1, b2, res, dy
 
 
-@pytest.mark.parametrize("cfg", [1, 2])
-@pytest.mark.parametrize("C,M", [(128, 1000), (256, 100)])
-def test_mlp_deep_ring(C, M, cfg, monkeypatch):
-    """csu_mlp_fwd_ex / csu_mlp_bwd_ex cfg 1 / 2 (the deep-ring kernels) with and without dropout into
-    guarded y, dh, g, dx: the criteria of test_mlp_fwd_deep_ring_vs_fp64 / test_mlp_bwd_deep_ring_vs_fp64."""
+@pytest.mark.parametrize("C,M", [(128, 1000)])
+def test_mlp_deep_ring(C, M, monkeypatch):
+    """The C = 128 product Mlp through the C ABI, csu_mlp_fwd_dp and csu_mlp_bwd_dp (the deep-ring backward), and the
+    per-panel backward csu_mlp_bwd_per_panel, with and without dropout + DropPath into guarded y, dh, g, dx: the fp64
+    criteria of test_mlp_bwd_deep_ring_vs_fp64, and the same for y against the fp64 Mlp + residual."""
     L_, rng, ops = mod("_lib"), mod("rng"), mod("ops")
     L, ptr, d = L_.lib(), L_.ptr, dev()
-    x, w1, w2, b1, b2, res, dy = _mlp_raw(C, M, C + M + cfg)
+    x, w1, w2, b1, b2, res, dy = _mlp_raw(C, M, C + M + 1)
     X, W1, W2, B1, B2, R, DY = (t.double() for t in (x, w1, w2, b1, b2, res, dy))
     st = L_.stream_ptr(d)
     for drop in (False, True):
@@ -1066,20 +1066,25 @@ def test_mlp_deep_ring(C, M, cfg, monkeypatch):
         y = ga.empty(M, C, dtype=F32, device=d)
         dh, gg = ga.empty(M, 4 * C, dtype=BF16, device=d), ga.empty(M, 4 * C, dtype=BF16, device=d)
         dx = ga.empty(M, C, dtype=BF16, device=d)
-        L_.check(L.csu_mlp_fwd_ex(M, C, ptr(xd), ptr(w1d), ptr(b1d), ptr(w2d), ptr(b2d), ptr(resd), ptr(y), ctypes.byref(md),
-                                  cfg, st), "mlp_fwd_ex")
-        L_.check(L.csu_mlp_bwd_ex(M, C, ptr(xd), ptr(dyd), ptr(w1d), ptr(b1d), ptr(w2d), ptr(dh), ptr(gg), ptr(dx),
-                                  ctypes.byref(md), cfg, st), "mlp_bwd_ex")
+        dh2, gg2 = ga.empty(M, 4 * C, dtype=BF16, device=d), ga.empty(M, 4 * C, dtype=BF16, device=d)
+        dx2 = ga.empty(M, C, dtype=BF16, device=d)
+        L_.check(L.csu_mlp_fwd_dp(M, C, ptr(xd), ptr(w1d), ptr(b1d), ptr(w2d), ptr(b2d), ptr(resd), ptr(y), ctypes.byref(md),
+                                  st), "mlp_fwd_dp")
+        L_.check(L.csu_mlp_bwd_dp(M, C, ptr(xd), ptr(dyd), ptr(w1d), ptr(b1d), ptr(w2d), ptr(dh), ptr(gg), ptr(dx),
+                                  ctypes.byref(md), st), "mlp_bwd_dp")
+        L_.check(L.csu_mlp_bwd_per_panel(M, C, ptr(xd), ptr(dyd), ptr(w1d), ptr(b1d), ptr(w2d), ptr(dh2), ptr(gg2), ptr(dx2),
+                                         ctypes.byref(md), st), "mlp_bwd_per_panel")
         torch.cuda.synchronize()
         verify(ga)
-        finite(y, dh, gg, dx)
+        finite(y, dh, gg, dx, dh2, gg2, dx2)
         ref = R + outm * ((F.gelu(X @ W1.T + B1) * mh) @ W2.T + B2)
         assert float((y.double().cpu() - ref).norm() / (ref - R).norm()) < 1e-2
         h = (X @ W1.T + B1).requires_grad_(True)
         gr = F.gelu(h)
         gr.backward((DY @ W2) * mh)
-        for name, got, r in zip(("dh", "g", "dx"), (dh, gg, dx), (h.grad, gr.detach() * mh, h.grad @ W1)):
-            assert float((got.double().cpu() - r).norm() / r.norm()) < 1e-2, (drop, name)
+        for outs in ((dh, gg, dx), (dh2, gg2, dx2)):
+            for name, got, r in zip(("dh", "g", "dx"), outs, (h.grad, gr.detach() * mh, h.grad @ W1)):
+                assert float((got.double().cpu() - r).norm() / r.norm()) < 1e-2, (drop, name)
 
 
 def test_mlp_bwd_wgrad_c64(monkeypatch):

@@ -1217,65 +1217,17 @@ def test_conv_c16_carafe4_encoder(B, H, W):
                                out.data_ptr(), 21, st) != 0
 
 
-@pytest.mark.parametrize("C,M", [(64, 4096), (128, 1000), (256, 4160), (256, 100)])
-@pytest.mark.parametrize("cfg", [1, 2])
-def test_mlp_fwd_deep_ring_vs_fp64(C, M, cfg):
-    """csu_mlp_fwd_ex cfg 1 / 2 (the deep-ring forward: 32-hidden weight chunks, waves split by tokens)
-    vs the fp64 Mlp + residual, without and with hidden / output dropout + DropPath (same masks as
-    the oracle composition); and it agrees with the per-panel kernel to bf16 rounding."""
+@pytest.mark.parametrize("C,M", [(128, 1000), (128, 64)])
+def test_mlp_bwd_deep_ring_vs_fp64(C, M):
+    """The C = 128 product backward, csu_mlp_bwd_dp's deep-ring kernel (M = 1000: 15 panels + 40 rows; M = 64: one
+    full panel) vs the fp64 composition: dh = (dy W2) gelu'(h) m_h, g = gelu(h) m_h, dx = dh W1, without and with
+    the hidden dropout mask; and it agrees with the per-panel backward (csu_mlp_bwd_per_panel) to bf16 rounding."""
     import ctypes
     from csu import rng
     from csu._lib import check, lib, ptr, stream_ptr
     from csu.ops import MlpDrop
     d = dev()
-    torch.manual_seed(C + M + cfg)
-    x = torch.randn(M, C, device=d).bfloat16()
-    w1 = (torch.randn(4 * C, C, device=d) * C ** -0.5).bfloat16()
-    w2 = (torch.randn(C, 4 * C, device=d) * (4 * C) ** -0.5).bfloat16()
-    b1, b2 = torch.randn(4 * C, device=d) * 0.1, torch.randn(C, device=d) * 0.1
-    res = torch.randn(M, C, device=d)
-    st = stream_ptr(d)
-    X, W1, W2, B1, B2, R = (t.double().cpu() for t in (x, w1, w2, b1, b2, res))
-    F = torch.nn.functional
-    for drop in (False, True):
-        if drop:
-            snap = torch.tensor([5, 2], dtype=torch.int64, device=d)
-            rps = max(1, M // 3)
-            rs = rng.droppath_scale(snap, 30, 0.3, -(-M // rps))
-            md = MlpDrop(snap, 21, 22, 0.3, rs, rps).c_struct()
-            mh = rng.dropout_mask(snap, 21, 0.3, M * 4 * C).view(M, 4 * C).double().cpu() / 0.7
-            mo = rng.dropout_mask(snap, 22, 0.3, M * C).view(M, C).double().cpu() / 0.7
-            outm = mo * rs.double().cpu()[torch.arange(M) // rps].view(M, 1)
-        else:
-            md = MlpDrop(None, 0, 0, 0.0).c_struct()
-            md.rows_per_sample = M
-            mh, outm = 1.0, 1.0
-        ys = []
-        for c in (cfg, 0):
-            y = torch.empty(M, C, device=d)
-            check(lib().csu_mlp_fwd_ex(M, C, ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(res), ptr(y),
-                                       ctypes.byref(md), c, st), "mlp_fwd_ex")
-            ys.append(y)
-        torch.cuda.synchronize()
-        ref = R + outm * ((F.gelu(X @ W1.T + B1) * mh) @ W2.T + B2)
-        err = float((ys[0].double().cpu() - ref).norm() / (ref - R).norm())
-        assert err < 1e-2, (drop, err)
-        d01 = float((ys[0] - ys[1]).double().norm() / (ys[1] - res).double().norm())
-        assert d01 < 1e-2, (drop, d01)
-
-
-@pytest.mark.parametrize("C,M", [(64, 4096), (128, 1000), (256, 4160), (256, 100)])
-@pytest.mark.parametrize("cfg", [1, 2])
-def test_mlp_bwd_deep_ring_vs_fp64(C, M, cfg):
-    """csu_mlp_bwd_ex cfg 1 / 2 (the deep-ring backward) vs the fp64 composition: dh = (dy W2)
-    gelu'(h) m_h, g = gelu(h) m_h, dx = dh W1, without and with the hidden dropout mask; and it agrees
-    with the per-panel backward (cfg 0) to bf16 rounding."""
-    import ctypes
-    from csu import rng
-    from csu._lib import check, lib, ptr, stream_ptr
-    from csu.ops import MlpDrop
-    d = dev()
-    torch.manual_seed(C + M + cfg + 7)
+    torch.manual_seed(C + M + 8)
     x = torch.randn(M, C, device=d).bfloat16()
     w1 = (torch.randn(4 * C, C, device=d) * C ** -0.5).bfloat16()
     w2 = (torch.randn(C, 4 * C, device=d) * (4 * C) ** -0.5).bfloat16()
@@ -1295,12 +1247,12 @@ def test_mlp_bwd_deep_ring_vs_fp64(C, M, cfg):
             md.rows_per_sample = M
             mh = torch.ones(M, 4 * C, dtype=torch.float64)
         outs = []
-        for c in (cfg, 0):
+        for entry in ("csu_mlp_bwd_dp", "csu_mlp_bwd_per_panel"):
             dh = torch.empty(M, 4 * C, device=d, dtype=torch.bfloat16)
             g = torch.empty_like(dh)
             dx = torch.empty(M, C, device=d, dtype=torch.bfloat16)
-            check(lib().csu_mlp_bwd_ex(M, C, ptr(x), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(dh), ptr(g), ptr(dx),
-                                       ctypes.byref(md), c, st), "mlp_bwd_ex")
+            check(getattr(lib(), entry)(M, C, ptr(x), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(dh), ptr(g), ptr(dx),
+                                        ctypes.byref(md), st), entry)
             outs.append((dh, g, dx))
         torch.cuda.synchronize()
         h = (X @ W1.T + B1).requires_grad_(True)
