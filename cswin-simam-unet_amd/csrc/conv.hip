@@ -13,6 +13,8 @@
 // Tiles: 64 x 64 outputs per 256-thread workgroup, 4 waves of one 32x32 MFMA tile, 32-deep K slices
 // gathered per 8-channel chunk (16-B loads when the gathered channel count is a multiple of 8).
 #include <cstdlib>
+#include <string>
+#include <vector>
 
 #include "common.hpp"
 #include "lds_dma.hpp"
@@ -934,10 +936,6 @@ KSplit ksplit_plan(const IG& g, int cus) {
     if ((long)n * g.M * g.Ncols * 4 > (32L << 20)) return KSplit{1, g.Kd};
     return KSplit{n, kper};
 }
-size_t ksplit_bytes(const IG& g, int cus) {
-    const KSplit k = ksplit_plan(g, cus);
-    return k.ksplit > 1 ? (size_t)k.ksplit * g.M * g.Ncols * 4 : 0;
-}
 
 // ---- bf16 implicit GEMM, v3 (Cs % 64 == 0, Ncols % BN == 0): persistent, LDS-DMA gathers ---------
 // Both operand images are filled by buffer_load ... lds (no VGPR round trip, lds_dma.hpp): the
@@ -1495,10 +1493,10 @@ int id_cus() {
 }
 
 template <int C>
-int id_launch(const IG& g, const void* src, const void* w, const float* bias, void* out, hipStream_t st) {
+int id_launch(const IG& g, const void* src, const void* w, const float* bias, void* out, hipStream_t st, int grid) {
     constexpr IDCfg c = kIDCfgs[C];
     if (g.Ncols % c.bn) return fail(CSU_E_ARG, "conv2d: Ncols not a multiple of the tile's BN");
-    igemm_dma<c.bm, c.bn, c.s, c.wm, c.wn, c.occ><<<dim3(c.occ * id_cus()), 64 * c.wm * c.wn, 0, st>>>(
+    igemm_dma<c.bm, c.bn, c.s, c.wm, c.wn, c.occ><<<dim3(grid), 64 * c.wm * c.wn, 0, st>>>(
         g, (const bf16*)src, (const bf16*)w, bias, (bf16*)out);
     return check_launch("conv2d (igemm_dma)");
 }
@@ -1522,34 +1520,51 @@ int id_pick(const IG& g, bool single = false) {
     return -1;
 }
 
-int id_run(int cfg, const IG& g, const void* src, const void* w, const float* bias, void* out, hipStream_t st) {
+int id_run(int cfg, const IG& g, const void* src, const void* w, const float* bias, void* out, hipStream_t st, int grid) {
     switch (cfg) {
-        case 0: return id_launch<0>(g, src, w, bias, out, st);
-        case 1: return id_launch<1>(g, src, w, bias, out, st);
-        case 2: return id_launch<2>(g, src, w, bias, out, st);
-        case 3: return id_launch<3>(g, src, w, bias, out, st);
-        case 4: return id_launch<4>(g, src, w, bias, out, st);
-        case 5: return id_launch<5>(g, src, w, bias, out, st);
-        case 6: return id_launch<6>(g, src, w, bias, out, st);
-        case 7: return id_launch<7>(g, src, w, bias, out, st);
-        case 8: return id_launch<8>(g, src, w, bias, out, st);
-        case 9: return id_launch<9>(g, src, w, bias, out, st);
-        case 10: return id_launch<10>(g, src, w, bias, out, st);
-        case 11: return id_launch<11>(g, src, w, bias, out, st);
+        case 0: return id_launch<0>(g, src, w, bias, out, st, grid);
+        case 1: return id_launch<1>(g, src, w, bias, out, st, grid);
+        case 2: return id_launch<2>(g, src, w, bias, out, st, grid);
+        case 3: return id_launch<3>(g, src, w, bias, out, st, grid);
+        case 4: return id_launch<4>(g, src, w, bias, out, st, grid);
+        case 5: return id_launch<5>(g, src, w, bias, out, st, grid);
+        case 6: return id_launch<6>(g, src, w, bias, out, st, grid);
+        case 7: return id_launch<7>(g, src, w, bias, out, st, grid);
+        case 8: return id_launch<8>(g, src, w, bias, out, st, grid);
+        case 9: return id_launch<9>(g, src, w, bias, out, st, grid);
+        case 10: return id_launch<10>(g, src, w, bias, out, st, grid);
+        case 11: return id_launch<11>(g, src, w, bias, out, st, grid);
         default: return fail(CSU_E_ARG, "conv2d: bad igemm_dma configuration");
     }
 }
 
-// n problems with equal Ncols and channel count (the phases of one input gradient, or one forward)
-// cfg: -1 per-shape choice (v3 where eligible), 0 the v2 kernel, 1 + k the v3 configuration k
-int launch_ig(const IG* gv, int n, const void* src, const void* w, const float* bias, void* out, hipStream_t st,
-              int cfg = -1, float* ws = nullptr, size_t ws_bytes = 0) {
-    IG4 gs{};
+// The plan of one launch group: n problems with equal Ncols and channel count (the phases of one
+// input gradient, or one forward).  ig_decide takes every decision, launch_ig only carries it out.
+// cfg: -1 per-shape choice (v3 where eligible), 0 the v2 kernel, 1 + k the v3 configuration k, 20 / 21
+// the halo64 / c16 kernels.  wgs: 0, or the grid of the persistent kernels.
+struct IGPlan {
+    int family;        // csu_conv_family
+    int n;
+    int idcfg[4];      // IGEMM_DMA: kIDCfgs index per problem
+    int grid[4];       // persistent kernels: workgroups per problem
+    bool flip;         // HALO64: the input-gradient form
+    bool narrow;       // IGEMM: 256 x 32 tiles
+    int vw;            // IGEMM: gather vector width
+    bool split;        // IGEMM: K split
+    KSplit ks;
+    unsigned gx, gy, gz;   // IGEMM grid
+};
+int wgs_check(int wgs) {
+    if (wgs < 0 || wgs % kXcds || wgs > 65536)
+        return fail(CSU_E_ARG, "conv2d: wgs must be 0 or a positive multiple of 8 (the kernels give each XCD gridDim.x / 8 workgroups)");
+    return 0;
+}
+int ig_decide(const IG* gv, int n, int cfg, int wgs, size_t ws_bytes, IGPlan* p) {
+    *p = IGPlan{};
+    p->n = n;
+    if (int e = wgs_check(wgs)) return e;
     long maxm = 0;
-    for (int i = 0; i < n; ++i) {
-        gs.g[i] = gv[i];
-        maxm = gv[i].M > maxm ? gv[i].M : maxm;
-    }
+    for (int i = 0; i < n; ++i) maxm = gv[i].M > maxm ? gv[i].M : maxm;
     const IG& g = gv[0];
     if ((long)g.B * g.Hs * g.Ws * g.Cs * 2 >= (1L << 31) || (long)g.Ncols * g.ldw * 2 >= (1L << 31) ||
         (long)g.B * g.OHo * g.OWo * g.Ncols * 2 >= (1L << 31))
@@ -1557,19 +1572,22 @@ int launch_ig(const IG* gv, int n, const void* src, const void* w, const float* 
     if ((cfg < 0 || cfg == kHalo64Cfg) && n == 1) {   // 64 -> 64 channel 3x3 stride-1 conv: the halo kernel
         const bool flip = g.sty == -1;
         if (halo64_ok(g, flip)) {
-            if (flip) conv3_halo64<true><<<dim3(id_cus()), 512, 0, st>>>(g.B, g.Hs, g.Ws, (const bf16*)src, (const bf16*)w, bias, (bf16*)out);
-            else conv3_halo64<false><<<dim3(id_cus()), 512, 0, st>>>(g.B, g.Hs, g.Ws, (const bf16*)src, (const bf16*)w, bias, (bf16*)out);
-            return check_launch("conv2d (halo64)");
+            p->family = CSU_CONV_HALO64;
+            p->flip = flip;
+            p->grid[0] = wgs ? wgs : id_cus();
+            return 0;
         }
     }
     if (cfg == kHalo64Cfg) return fail(CSU_E_ARG, "conv2d: halo64 configuration not eligible");
     if ((cfg < 0 || cfg == kC16Cfg) && n == 1 && c16_ok(g)) {   // 16 -> 144 channel 3x3 conv (CARAFE4 encoder)
-        conv3_c16<144><<<dim3(2 * id_cus()), 256, 0, st>>>(g.B, g.Hs, g.Ws, (const bf16*)src, (const bf16*)w, bias, (bf16*)out);
-        return check_launch("conv2d (c16)");
+        p->family = CSU_CONV_C16;
+        p->grid[0] = wgs ? wgs : 2 * id_cus();
+        return 0;
     }
     if ((cfg < 0 || cfg == kC16Cfg) && n == 1 && c16d_ok(g)) {   // its input gradient (144 -> 16)
-        conv3_c16d<<<dim3(id_cus()), 256, 0, st>>>(g.B, g.Hs, g.Ws, (const bf16*)src, (const bf16*)w, (bf16*)out);
-        return check_launch("conv2d (c16d)");
+        p->family = CSU_CONV_C16D;
+        p->grid[0] = wgs ? wgs : id_cus();
+        return 0;
     }
     if (cfg == kC16Cfg) return fail(CSU_E_ARG, "conv2d: c16 configuration not eligible");
     if (cfg > 0) {   // forced v3 configuration: every phase must be eligible for it
@@ -1577,9 +1595,11 @@ int launch_ig(const IG* gv, int n, const void* src, const void* w, const float* 
         if (k >= kIDNCfg) return fail(CSU_E_ARG, "conv2d: bad igemm_dma configuration");
         for (int i = 0; i < n; ++i)
             if (!id_eligible(gv[i]) || gv[i].Ncols % kIDCfgs[k].bn) return fail(CSU_E_ARG, "conv2d: igemm_dma configuration not eligible");
-        for (int i = 0; i < n; ++i)
-            if (gv[i].M > 0)
-                if (int e = id_run(k, gv[i], src, w, bias, out, st)) return e;
+        p->family = CSU_CONV_IGEMM_DMA;
+        for (int i = 0; i < n; ++i) {
+            p->idcfg[i] = k;
+            p->grid[i] = wgs ? wgs : kIDCfgs[k].occ * id_cus();
+        }
         return 0;
     }
     if (cfg < 0) {   // per-shape choice: v3 (each phase its own tile) when every phase has one
@@ -1587,40 +1607,69 @@ int launch_ig(const IG* gv, int n, const void* src, const void* w, const float* 
         bool all = true;
         for (int i = 0; i < n; ++i) all = all && (pk[i] = id_pick(gv[i], n == 1)) >= 0;
         if (all) {
-            for (int i = 0; i < n; ++i)
-                if (gv[i].M > 0)
-                    if (int e = id_run(pk[i], gv[i], src, w, bias, out, st)) return e;
+            p->family = CSU_CONV_IGEMM_DMA;
+            for (int i = 0; i < n; ++i) {
+                p->idcfg[i] = pk[i];
+                p->grid[i] = wgs ? wgs : kIDCfgs[pk[i]].occ * id_cus();
+            }
             return 0;
         }
     }
-    const int vw = g.Cs % 8 == 0 ? 8 : 4;
-    const bool narrow = g.Ncols <= 32;
-    const int BM = narrow ? 256 : 128, BN = narrow ? 32 : 64;
-    const KSplit ks = n == 1 && cfg < 0 && ws ? ksplit_plan(g, id_cus()) : KSplit{1, g.Kd};
-    const bool split = ks.ksplit > 1 && ws_bytes >= (size_t)ks.ksplit * g.M * g.Ncols * 4;
-    gs.ksplit = split ? ks.ksplit : 1;
-    gs.kper = split ? ks.kper : g.Kd;
-    gs.slab = split ? ws : nullptr;
-    const dim3 grid((unsigned)((maxm + BM - 1) / BM), (g.Ncols + BN - 1) / BN, split ? ks.ksplit : n);
+    p->family = CSU_CONV_IGEMM;
+    p->vw = g.Cs % 8 == 0 ? 8 : 4;
+    p->narrow = g.Ncols <= 32;
+    const int BM = p->narrow ? 256 : 128, BN = p->narrow ? 32 : 64;
+    p->ks = n == 1 && cfg < 0 && ws_bytes ? ksplit_plan(g, id_cus()) : KSplit{1, g.Kd};
+    p->split = p->ks.ksplit > 1 && ws_bytes >= (size_t)p->ks.ksplit * g.M * g.Ncols * 4;
+    if (!p->split) p->ks = KSplit{1, g.Kd};
+    p->gx = (unsigned)((maxm + BM - 1) / BM);
+    p->gy = (unsigned)((g.Ncols + BN - 1) / BN);
+    p->gz = (unsigned)(p->split ? p->ks.ksplit : n);
+    return 0;
+}
+
+int launch_ig(const IG* gv, int n, const void* src, const void* w, const float* bias, void* out, hipStream_t st,
+              const IGPlan& p, float* ws) {
+    const IG& g = gv[0];
     const bf16* s = (const bf16*)src;
     const bf16* wb = (const bf16*)w;
     bf16* o = (bf16*)out;
-    if (narrow) {
-        if (vw == 8) igemm_bf16<32, 8><<<grid, NT, 0, st>>>(gs, s, wb, bias, o);
+    switch (p.family) {
+        case CSU_CONV_HALO64:
+            if (p.flip) conv3_halo64<true><<<dim3(p.grid[0]), 512, 0, st>>>(g.B, g.Hs, g.Ws, s, wb, bias, o);
+            else conv3_halo64<false><<<dim3(p.grid[0]), 512, 0, st>>>(g.B, g.Hs, g.Ws, s, wb, bias, o);
+            return check_launch("conv2d (halo64)");
+        case CSU_CONV_C16:
+            conv3_c16<144><<<dim3(p.grid[0]), 256, 0, st>>>(g.B, g.Hs, g.Ws, s, wb, bias, o);
+            return check_launch("conv2d (c16)");
+        case CSU_CONV_C16D:
+            conv3_c16d<<<dim3(p.grid[0]), 256, 0, st>>>(g.B, g.Hs, g.Ws, s, wb, o);
+            return check_launch("conv2d (c16d)");
+        case CSU_CONV_IGEMM_DMA:
+            for (int i = 0; i < n; ++i)
+                if (gv[i].M > 0)
+                    if (int e = id_run(p.idcfg[i], gv[i], src, w, bias, out, st, p.grid[i])) return e;
+            return 0;
+        default: break;
+    }
+    IG4 gs{};
+    for (int i = 0; i < n; ++i) gs.g[i] = gv[i];
+    gs.ksplit = p.ks.ksplit;
+    gs.kper = p.ks.kper;
+    gs.slab = p.split ? ws : nullptr;
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (p.narrow) {
+        if (p.vw == 8) igemm_bf16<32, 8><<<grid, NT, 0, st>>>(gs, s, wb, bias, o);
         else igemm_bf16<32, 4><<<grid, NT, 0, st>>>(gs, s, wb, bias, o);
     } else {
-        if (vw == 8) igemm_bf16<64, 8><<<grid, NT, 0, st>>>(gs, s, wb, bias, o);
+        if (p.vw == 8) igemm_bf16<64, 8><<<grid, NT, 0, st>>>(gs, s, wb, bias, o);
         else igemm_bf16<64, 4><<<grid, NT, 0, st>>>(gs, s, wb, bias, o);
     }
-    if (split) {
+    if (p.split) {
         const long nthr = g.M * (g.Ncols / 4);
-        conv_split_reduce<<<(unsigned)((nthr + NT - 1) / NT), NT, 0, st>>>(g, ks.ksplit, ws, bias, o);
+        conv_split_reduce<<<(unsigned)((nthr + NT - 1) / NT), NT, 0, st>>>(g, p.ks.ksplit, ws, bias, o);
     }
     return check_launch("conv2d (igemm)");
-}
-int launch_ig(const IG& g, const void* src, const void* w, const float* bias, void* out, hipStream_t st, int cfg = -1,
-              float* ws = nullptr, size_t ws_bytes = 0) {
-    return launch_ig(&g, 1, src, w, bias, out, st, cfg, ws, ws_bytes);
 }
 IG ig_forward(const csu_conv_geom& c) {
     IG g{};
@@ -1767,6 +1816,38 @@ size_t wgrad_ws(const csu_conv_geom* gm, int pick) {
     return (size_t)p.chunks * slab * sizeof(float) + stage + colsum_workspace(p.chunks, slab, CSU_F32);
 }
 
+// Every decision of a weight-gradient call (conv_wgrad_impl launches it, csu_conv2d_plan reports it)
+struct WgradPlanI {
+    int pick;      // wd_pick
+    WPl p;
+    long total;    // rows (halo picks: 64-pixel segments) the chunks divide
+    size_t ws;
+    int v2;        // csu_conv_wgrad_v2: the kernel behind pick -1
+};
+int wgrad_decide(const csu_conv_geom* gm, int dtype, int cfg, int csplit, WgradPlanI* o) {
+    if (int e = check_geo(gm)) return e;
+    if (csplit && (dtype != CSU_BF16 || !csu_conv2d_split_ok(gm, csplit)))
+        return fail(CSU_E_UNSUPPORTED, "conv2d_wgrad_split: not eligible");
+    o->pick = wd_pick(gm, dtype, cfg);
+    if (o->pick == -2) return fail(CSU_E_ARG, "conv2d_wgrad: configuration not eligible (bf16, C % 8 == 0, N % 8 == 0)");
+    if (csplit && o->pick != kHalo64 && o->pick != kHalo128)
+        return fail(CSU_E_UNSUPPORTED, "conv2d_wgrad: two-source input needs the halo kernel");
+    if (dtype != CSU_BF16 && dtype != CSU_F32) return fail(CSU_E_ARG, "conv2d_wgrad: bad dtype");
+    o->v2 = CSU_WGRAD_V2_NONE;
+    if (o->pick < 0) {   // v2: bf16 MFMA kernel (32-bit offsets, 8- or 4-wide dy), else the gathering kernel
+        const bool vec = gm->C % 8 == 0;
+        const bool small = (long)gm->B * gm->H * gm->W * gm->C * 2 < (1L << 31) && (long)gm->B * gm->OH * gm->OW * gm->N * 2 < (1L << 31);
+        if (dtype == CSU_F32) o->v2 = vec ? CSU_WGRAD_V2_F32 : CSU_WGRAD_V2_F32_SCALAR;
+        else if (vec && gm->N % 8 == 0 && small) o->v2 = CSU_WGRAD_V2_BF16;
+        else if (vec && gm->N % 4 == 0 && small) o->v2 = CSU_WGRAD_V2_BF16_N4;
+        else o->v2 = vec ? CSU_WGRAD_V2_BF16_WIDE : CSU_WGRAD_V2_BF16_SCALAR;
+    }
+    o->p = wplan_any(gm, o->pick);
+    o->total = o->pick == kHalo64 || o->pick == kHalo128 ? (long)gm->B * gm->OH * (gm->OW / 64) : (long)gm->B * gm->OH * gm->OW;
+    o->ws = wgrad_ws(gm, o->pick);
+    return 0;
+}
+
 template <int C>
 void wd_launch(const Geo& g, long M, int N, int K, const WPl& p, const void* x, const void* dy, float* part, hipStream_t st) {
     constexpr WDCfg c = kWDCfgs[C];
@@ -1811,53 +1892,188 @@ int launch_gemm(const Geo& g, long M, int Ncols, int Kdim, const void* src, cons
 
 using namespace csu;
 
+// Every decision of a forward (op 0) or input-gradient (op 1) call.  conv_decide is the one function
+// that takes them: conv_exec carries its plan out and csu_conv2d_plan reports it.
+struct ConvGroup {
+    int first, n;   // problems ph[first .. first + n) go out as one launch group
+    bool ws;        // the group may use the caller's workspace (K split)
+    IGPlan p;
+};
+struct ConvPlanI {
+    bool scalar = false;   // conv_gemm: fp32, or bf16 with gathered channels % 4 != 0
+    bool vec = false;
+    long M = 0;
+    int Ncols = 0, Kdim = 0;
+    int c_split = 0;
+    std::vector<IG> ph;
+    std::vector<ConvGroup> groups;
+};
+
+static int conv_decide(int op, const csu_conv_geom* gm, int dtype, int cfg, int wgs, int c_split, void* second,
+                       size_t ws_bytes, ConvPlanI* P) {
+    if (op != 0 && op != 1) return fail(CSU_E_ARG, "conv2d: op must be 0 (forward) or 1 (input gradient)");
+    const char* nm = op == 0 ? "conv2d_fwd" : "conv2d_dgrad";
+    if (int e = check_geo(gm)) return e;
+    if (int e = wgs_check(wgs)) return e;
+    if (c_split && (dtype != CSU_BF16 || !csu_conv2d_split_ok(gm, c_split)))
+        return fail(CSU_E_UNSUPPORTED, std::string(nm) + "_split: not eligible");
+    P->c_split = c_split;
+    const Geo g = to_geo(gm);
+    const int gathered = op == 0 ? g.C : g.N;   // channels of the gathered operand
+    if (dtype == CSU_BF16 && gathered % 4 == 0) {
+        if (op == 0) {
+            IG ig = ig_forward(*gm);
+            ig.csplit = c_split;
+            ig.src2 = c_split ? (const bf16*)second : nullptr;
+            P->ph.push_back(ig);
+        } else {
+            for (int py = 0; py < g.s; ++py)
+                for (int px = 0; px < g.s; ++px) {
+                    IG ig = ig_dgrad_phase(*gm, py, px);
+                    if (ig.M == 0) continue;
+                    ig.nsplit = c_split;
+                    ig.out2 = c_split ? (bf16*)second : nullptr;
+                    P->ph.push_back(ig);
+                }
+        }
+        const int np = (int)P->ph.size();
+        for (int first = 0; first < np; first += 4) {   // stride > 2: groups of four phases
+            ConvGroup gr{};
+            gr.first = first;
+            gr.n = np - first < 4 ? np - first : 4;
+            gr.ws = gr.n == 1 && first + 1 == np;   // a one-problem launch may split K
+            if (int e = ig_decide(&P->ph[first], gr.n, cfg, wgs, gr.ws ? ws_bytes : 0, &gr.p)) return e;
+            P->groups.push_back(gr);
+        }
+        return 0;
+    }
+    if (cfg > 0) return fail(CSU_E_ARG, std::string(nm) + ": igemm_dma needs bf16 with gathered channels % 64 == 0");
+    if (dtype != CSU_BF16 && dtype != CSU_F32) return fail(CSU_E_ARG, std::string(nm) + ": bad dtype");
+    P->scalar = true;
+    P->vec = gathered % 8 == 0;
+    P->M = op == 0 ? (long)g.B * g.OH * g.OW : (long)g.B * g.H * g.W;
+    P->Ncols = op == 0 ? g.N : g.C;
+    P->Kdim = g.KH * g.KW * gathered;
+    return 0;
+}
+
+static int conv_exec(int op, const csu_conv_geom* gm, int dtype, const void* src, const void* w, const float* bias, void* out,
+                     void* second, int c_split, int cfg, int wgs, void* ws, size_t ws_bytes, void* stream) {
+    const char* nm = op == 0 ? "conv2d_fwd" : "conv2d_dgrad";
+    if (int e = check_geo(gm)) return e;
+    if (!c_split && (!src || !w || !out)) return fail(CSU_E_ARG, std::string(nm) + ": null buffer");
+    ConvPlanI P;
+    if (int e = conv_decide(op, gm, dtype, cfg, wgs, c_split, second, ws ? ws_bytes : 0, &P)) return e;
+    if (c_split && (!src || !w || !out || !second)) return fail(CSU_E_ARG, std::string(nm) + "_split: null buffer");
+    hipStream_t st = as_stream(stream);
+    if (P.scalar) {
+        const Geo g = to_geo(gm);
+        if (op == 0) {
+            if (dtype == CSU_BF16) return launch_gemm<bf16, 0>(g, P.M, P.Ncols, P.Kdim, src, w, bias, out, P.vec, st);
+            return launch_gemm<float, 0>(g, P.M, P.Ncols, P.Kdim, src, w, bias, out, P.vec, st);
+        }
+        if (dtype == CSU_BF16) return launch_gemm<bf16, 1>(g, P.M, P.Ncols, P.Kdim, src, w, bias, out, P.vec, st);
+        return launch_gemm<float, 1>(g, P.M, P.Ncols, P.Kdim, src, w, bias, out, P.vec, st);
+    }
+    for (const ConvGroup& gr : P.groups)
+        if (int e = launch_ig(&P.ph[gr.first], gr.n, src, w, bias, out, st, gr.p, gr.ws ? (float*)ws : nullptr)) return e;
+    return 0;
+}
+
 static int conv_fwd_impl(const csu_conv_geom* gm, int dtype, const void* x, const void* w_ohwi, const float* bias, void* out,
                          int cfg, void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
-    if (int e = check_geo(gm)) return e;
-    if (!x || !w_ohwi || !out) return fail(CSU_E_ARG, "conv2d_fwd: null buffer");
-    const Geo g = to_geo(gm);
-    const long M = (long)g.B * g.OH * g.OW;
-    const int K = g.KH * g.KW * g.C;
-    const bool vec = g.C % 8 == 0;
-    hipStream_t st = as_stream(stream);
-    if (dtype == CSU_BF16 && g.C % 4 == 0) return launch_ig(ig_forward(*gm), x, w_ohwi, bias, out, st, cfg, (float*)ws, ws_bytes);
-    if (cfg > 0) return fail(CSU_E_ARG, "conv2d_fwd: igemm_dma needs bf16 with C % 64 == 0");
-    if (dtype == CSU_BF16) return launch_gemm<bf16, 0>(g, M, g.N, K, x, w_ohwi, bias, out, vec, st);
-    if (dtype == CSU_F32) return launch_gemm<float, 0>(g, M, g.N, K, x, w_ohwi, bias, out, vec, st);
-    return fail(CSU_E_ARG, "conv2d_fwd: bad dtype");
+    return conv_exec(0, gm, dtype, x, w_ohwi, bias, out, nullptr, 0, cfg, 0, ws, ws_bytes, stream);
 }
-
 static int conv_dgrad_impl(const csu_conv_geom* gm, int dtype, const void* dy, const void* w_ihwo, const float* bias, void* dx,
                            int cfg, void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
-    if (int e = check_geo(gm)) return e;
-    if (!dy || !w_ihwo || !dx) return fail(CSU_E_ARG, "conv2d_dgrad: null buffer");
-    const Geo g = to_geo(gm);
-    const long M = (long)g.B * g.H * g.W;
-    const int K = g.KH * g.KW * g.N;
-    const bool vec = g.N % 8 == 0;
-    hipStream_t st = as_stream(stream);
-    if (dtype == CSU_BF16 && g.N % 4 == 0) {
-        IG ph[4];
-        int np = 0;
-        for (int py = 0; py < g.s; ++py)
-            for (int px = 0; px < g.s; ++px) {
-                const IG ig = ig_dgrad_phase(*gm, py, px);
-                if (ig.M == 0) continue;
-                if (np == 4) {   // stride > 2: flush
-                    if (int e = launch_ig(ph, np, dy, w_ihwo, bias, dx, st, cfg)) return e;
-                    np = 0;
-                }
-                ph[np++] = ig;
-            }
-        if (np == 1) return launch_ig(ph, 1, dy, w_ihwo, bias, dx, st, cfg, (float*)ws, ws_bytes);
-        return np ? launch_ig(ph, np, dy, w_ihwo, bias, dx, st, cfg) : 0;
-    }
-    if (cfg > 0) return fail(CSU_E_ARG, "conv2d_dgrad: igemm_dma needs bf16 with N % 64 == 0");
-    if (dtype == CSU_BF16) return launch_gemm<bf16, 1>(g, M, g.C, K, dy, w_ihwo, bias, dx, vec, st);
-    if (dtype == CSU_F32) return launch_gemm<float, 1>(g, M, g.C, K, dy, w_ihwo, bias, dx, vec, st);
-    return fail(CSU_E_ARG, "conv2d_dgrad: bad dtype");
+    return conv_exec(1, gm, dtype, dy, w_ihwo, bias, dx, nullptr, 0, cfg, 0, ws, ws_bytes, stream);
 }
 
+// tiles per workgroup of the persistent kernels' XCD-contiguous ranges (igemm_dma, conv3_halo64,
+// conv3_c16, conv3_c16d: XCD x owns q + (x < rem) tiles, its workgroup kk every nloc-th of them)
+static void persistent_counts(long tiles, int grid, int* tmax, int* tmin, int* idle) {
+    const long nloc = grid / kXcds, q = tiles / kXcds, rem = tiles % kXcds;
+    *tmax = 0;
+    *tmin = 1 << 30;
+    *idle = 0;
+    for (long x = 0; x < kXcds; ++x) {
+        const long cnt = q + (x < rem ? 1 : 0);
+        const int hi = (int)((cnt + nloc - 1) / nloc);                                    // kk = 0
+        const int lo = nloc - 1 < cnt ? (int)((cnt - (nloc - 1) + nloc - 1) / nloc) : 0;   // kk = nloc - 1
+        *tmax = hi > *tmax ? hi : *tmax;
+        *tmin = lo < *tmin ? lo : *tmin;
+        *idle += (int)(nloc > cnt ? nloc - cnt : 0);
+    }
+}
+
+static void conv_report(const csu_conv_geom* gm, const ConvPlanI& P, csu_conv_plan* o) {
+    *o = csu_conv_plan{};
+    o->cus = id_cus();
+    o->two_source = P.c_split;
+    o->ksplit = 1;
+    o->wgrad_pick = -1;
+    int np = 0;
+    auto phase = [&](int fam, int cfg, int bm, int bn, int ring, long rows, long tiles, int nk, int grid, bool persistent) {
+        int tmax = 1, tmin = grid > tiles ? 0 : 1, idle = grid > tiles ? (int)(grid - tiles) : 0;
+        if (persistent) persistent_counts(tiles, grid, &tmax, &tmin, &idle);
+        if (np == 0) {
+            o->wg_tiles_max = tmax;
+            o->wg_tiles_min = tmin;
+        }
+        o->wg_tiles_max = tmax > o->wg_tiles_max ? tmax : o->wg_tiles_max;
+        o->wg_tiles_min = tmin < o->wg_tiles_min ? tmin : o->wg_tiles_min;
+        o->wgs_idle += idle;
+        if (np < CSU_CONV_PLAN_PHASES) {
+            o->phase_family[np] = fam; o->phase_cfg[np] = cfg; o->phase_bm[np] = bm; o->phase_bn[np] = bn;
+            o->phase_ring[np] = ring; o->phase_rows[np] = rows; o->phase_tiles[np] = tiles; o->phase_nk[np] = nk;
+            o->phase_grid[np] = grid; o->phase_tiles_max[np] = tmax; o->phase_tiles_min[np] = tmin;
+            o->phase_idle[np] = idle; o->phase_xcd_rem[np] = persistent ? (int)(tiles % kXcds) : 0;
+        }
+        ++np;
+    };
+    if (P.scalar) {
+        const long tiles = ((P.M + TBM - 1) / TBM) * ((P.Ncols + TBN - 1) / TBN);
+        o->family = CSU_CONV_GEMM;
+        o->gemm_vec = P.vec;
+        o->kper = P.Kdim;
+        phase(CSU_CONV_GEMM, -1, TBM, TBN, 0, P.M, tiles, (P.Kdim + TBK - 1) / TBK, (int)tiles, false);
+        o->n_problems = 1;
+        return;
+    }
+    for (const ConvGroup& gr : P.groups)
+        for (int i = 0; i < gr.n; ++i) {
+            const IG& g = P.ph[gr.first + i];
+            const IGPlan& p = gr.p;
+            switch (p.family) {
+                case CSU_CONV_HALO64:
+                    phase(p.family, kHalo64Cfg, 128, 64, 2, g.M, (long)g.B * (g.Hs / 2) * (g.Ws / 64), 1, p.grid[i], true);
+                    break;
+                case CSU_CONV_C16:
+                case CSU_CONV_C16D:
+                    phase(p.family, kC16Cfg, 64, g.Ncols, 2, g.M, (long)g.B * g.Hs * (g.Ws / 64), 1, p.grid[i], true);
+                    break;
+                case CSU_CONV_IGEMM_DMA: {
+                    const IDCfg& c = kIDCfgs[p.idcfg[i]];
+                    phase(p.family, 1 + p.idcfg[i], c.bm, c.bn, c.s, g.M, ((g.M + c.bm - 1) / c.bm) * (g.Ncols / c.bn),
+                          g.Kd / 64, p.grid[i], true);
+                    break;
+                }
+                default: {
+                    const int BM = p.narrow ? 256 : 128, BN = p.narrow ? 32 : 64;
+                    const long tiles = ((g.M + BM - 1) / BM) * p.gy * (p.split ? p.ks.ksplit : 1);
+                    phase(p.family, 0, BM, BN, 0, g.M, tiles, (p.ks.kper + 63) / 64,
+                          (int)(p.gx * p.gy * (p.split ? p.ks.ksplit : 1)), false);
+                    o->ksplit = p.ks.ksplit;
+                    o->kper = p.ks.kper;
+                    o->v2_bn = BN;
+                    o->v2_vw = p.vw;
+                    break;
+                }
+            }
+        }
+    o->n_problems = np;
+    o->family = np ? o->phase_family[0] : CSU_CONV_IGEMM;
+}
 extern "C" int csu_conv2d_fwd(const csu_conv_geom* gm, int dtype, const void* x, const void* w_ohwi, const float* bias,
                               void* out, void* stream) {
     return conv_fwd_impl(gm, dtype, x, w_ohwi, bias, out, -1, stream);
@@ -1868,17 +2084,16 @@ extern "C" int csu_conv2d_dgrad(const csu_conv_geom* gm, int dtype, const void* 
     return conv_dgrad_impl(gm, dtype, dy, w_ihwo, bias, dx, -1, stream);
 }
 
-// workspace of the K-split v2 launches (one-problem bf16 convs with few tiles; 0: never split)
+// workspace of the K-split v2 launches (one-problem bf16 convs with few tiles; 0: never split): what the
+// plan would split into, given any workspace
 extern "C" size_t csu_conv2d_workspace(int op, const csu_conv_geom* gm, int dtype) {
     if (check_geo(gm) || dtype != CSU_BF16 || (op != 0 && op != 1)) return 0;
-    if (op == 0) {
-        if (gm->C % 4) return 0;
-        const IG g = ig_forward(*gm);
-        return id_pick(g, true) >= 0 ? 0 : ksplit_bytes(g, id_cus());
-    }
-    if (gm->N % 4 || gm->stride != 1) return 0;
-    const IG g = ig_dgrad_phase(*gm, 0, 0);
-    return id_pick(g, true) >= 0 ? 0 : ksplit_bytes(g, id_cus());
+    ConvPlanI P;
+    if (conv_decide(op, gm, dtype, -1, 0, 0, nullptr, ~(size_t)0, &P) || P.scalar || P.groups.empty()) return 0;
+    const ConvGroup& gr = P.groups.back();
+    if (!gr.ws || !gr.p.split) return 0;
+    const IG& g = P.ph[gr.first];
+    return (size_t)gr.p.ks.ksplit * g.M * g.Ncols * 4;
 }
 
 extern "C" int csu_conv2d_fwd_ws(const csu_conv_geom* gm, int dtype, const void* x, const void* w_ohwi, const float* bias,
@@ -1918,37 +2133,33 @@ static int conv_wgrad_impl(const csu_conv_geom* gm, int dtype, const void* x, co
                            void* workspace, size_t ws_bytes, int cfg, void* stream, const void* x2 = nullptr, int csplit = 0) {
     if (int e = check_geo(gm)) return e;
     if (!x || !dy || !dw_db) return fail(CSU_E_ARG, "conv2d_wgrad: null buffer");
-    const int pick = wd_pick(gm, dtype, cfg);
-    if (pick == -2) return fail(CSU_E_ARG, "conv2d_wgrad: configuration not eligible (bf16, C % 8 == 0, N % 8 == 0)");
-    if (csplit && pick != kHalo64 && pick != kHalo128)
-        return fail(CSU_E_UNSUPPORTED, "conv2d_wgrad: two-source input needs the halo kernel");
-    if (!workspace || ws_bytes < wgrad_ws(gm, pick)) return fail(CSU_E_WORKSPACE, "conv2d_wgrad: workspace");
+    WgradPlanI wp;
+    if (int e = wgrad_decide(gm, dtype, cfg, csplit, &wp)) return e;
+    const int pick = wp.pick;
+    if (!workspace || ws_bytes < wp.ws) return fail(CSU_E_WORKSPACE, "conv2d_wgrad: workspace");
     if (creal > gm->C) return fail(CSU_E_ARG, "conv2d_wgrad: c_real > C");
     const Geo g = to_geo(gm);
     const long M = (long)g.B * g.OH * g.OW;
     const int K = g.KH * g.KW * g.C;
-    const WPl p = wplan_any(gm, pick);
+    const WPl p = wp.p;
     const long used = (long)g.N * K + g.N;
     const long slab = (used + 3) & ~3L;
     float* part = (float*)workspace;
     const dim3 grid((g.N + TBN - 1) / TBN, (K + TBN - 1) / TBN, p.chunks);
-    const bool vec = g.C % 8 == 0;
     hipStream_t st = as_stream(stream);
     if (pick >= 0) {
         wd_run(pick, g, M, g.N, K, p, x, dy, part, st, x2, csplit);
-    } else if (dtype == CSU_BF16) {
-        const bool small = (long)g.B * g.H * g.W * g.C * 2 < (1L << 31) && M * g.N * 2 < (1L << 31);   // 32-bit offsets
-        if (vec && g.N % 8 == 0 && small)
-            conv_wgrad_bf16<false><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const bf16*)x, (const bf16*)dy, part);
-        else if (vec && g.N % 4 == 0 && small)
-            conv_wgrad_bf16<true><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const bf16*)x, (const bf16*)dy, part);
-        else if (vec) conv_wgrad_kernel<bf16, true><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const bf16*)x, (const bf16*)dy, part);
-        else conv_wgrad_kernel<bf16, false><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const bf16*)x, (const bf16*)dy, part);
-    } else if (dtype == CSU_F32) {
-        if (vec) conv_wgrad_kernel<float, true><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const float*)x, (const float*)dy, part);
-        else conv_wgrad_kernel<float, false><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const float*)x, (const float*)dy, part);
     } else {
-        return fail(CSU_E_ARG, "conv2d_wgrad: bad dtype");
+        const bf16* xb = (const bf16*)x;
+        const bf16* dyb = (const bf16*)dy;
+        switch (wp.v2) {
+            case CSU_WGRAD_V2_BF16: conv_wgrad_bf16<false><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, xb, dyb, part); break;
+            case CSU_WGRAD_V2_BF16_N4: conv_wgrad_bf16<true><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, xb, dyb, part); break;
+            case CSU_WGRAD_V2_BF16_WIDE: conv_wgrad_kernel<bf16, true><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, xb, dyb, part); break;
+            case CSU_WGRAD_V2_BF16_SCALAR: conv_wgrad_kernel<bf16, false><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, xb, dyb, part); break;
+            case CSU_WGRAD_V2_F32: conv_wgrad_kernel<float, true><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const float*)x, (const float*)dy, part); break;
+            default: conv_wgrad_kernel<float, false><<<grid, NT, 0, st>>>(g, M, g.N, K, p.rpc, (const float*)x, (const float*)dy, part); break;
+        }
     }
     if (int e = check_launch("conv2d_wgrad")) return e;
     if (creal > 0) {   // chunk sums written straight into torch's OIHW layout (+ db)
@@ -1989,31 +2200,48 @@ extern "C" int csu_conv2d_split_ok(const csu_conv_geom* gm, int c_split) {
 
 extern "C" int csu_conv2d_fwd_split(const csu_conv_geom* gm, int dtype, const void* x, const void* x2, int c_split,
                                     const void* w_ohwi, const float* bias, void* y, void* stream) {
-    if (int e = check_geo(gm)) return e;
-    if (dtype != CSU_BF16 || !csu_conv2d_split_ok(gm, c_split)) return fail(CSU_E_UNSUPPORTED, "conv2d_fwd_split: not eligible");
-    if (!x || !x2 || !w_ohwi || !y) return fail(CSU_E_ARG, "conv2d_fwd_split: null buffer");
-    IG g = ig_forward(*gm);
-    g.csplit = c_split;
-    g.src2 = (const bf16*)x2;
-    return launch_ig(g, x, w_ohwi, bias, y, as_stream(stream));
+    if (c_split == 0) return fail(CSU_E_UNSUPPORTED, "conv2d_fwd_split: not eligible");
+    return conv_exec(0, gm, dtype, x, w_ohwi, bias, y, const_cast<void*>(x2), c_split, -1, 0, nullptr, 0, stream);
 }
 
 extern "C" int csu_conv2d_dgrad_split(const csu_conv_geom* gm, int dtype, const void* dy, const void* w_ihwo, void* dx, void* dx2,
                                       int c_split, void* stream) {
-    if (int e = check_geo(gm)) return e;
-    if (dtype != CSU_BF16 || !csu_conv2d_split_ok(gm, c_split)) return fail(CSU_E_UNSUPPORTED, "conv2d_dgrad_split: not eligible");
-    if (!dy || !w_ihwo || !dx || !dx2) return fail(CSU_E_ARG, "conv2d_dgrad_split: null buffer");
-    IG ph[4];
-    int np = 0;
-    for (int py = 0; py < gm->stride; ++py)
-        for (int px = 0; px < gm->stride; ++px) {
-            IG ig = ig_dgrad_phase(*gm, py, px);
-            if (ig.M == 0) continue;
-            ig.nsplit = c_split;
-            ig.out2 = (bf16*)dx2;
-            ph[np++] = ig;
-        }
-    return np ? launch_ig(ph, np, dy, w_ihwo, nullptr, dx, as_stream(stream)) : 0;
+    if (c_split == 0) return fail(CSU_E_UNSUPPORTED, "conv2d_dgrad_split: not eligible");
+    return conv_exec(1, gm, dtype, dy, w_ihwo, nullptr, dx, dx2, c_split, -1, 0, nullptr, 0, stream);
+}
+
+extern "C" int csu_conv2d_ex2(int op, const csu_conv_geom* gm, int dtype, const void* src, const void* w, const float* bias,
+                              void* out, void* second, int c_split, int cfg, int wgs, void* workspace, size_t ws_bytes,
+                              void* stream) {
+    if (op != 0 && op != 1) return fail(CSU_E_ARG, "conv2d_ex2: op must be 0 (forward) or 1 (input gradient)");
+    return conv_exec(op, gm, dtype, src, w, bias, out, second, c_split, cfg, wgs, workspace, ws_bytes, stream);
+}
+
+extern "C" int csu_conv2d_plan(int op, const csu_conv_geom* gm, int dtype, int cfg, int wgs, int c_split, size_t ws_bytes,
+                               csu_conv_plan* out) {
+    if (!out) return fail(CSU_E_ARG, "conv2d_plan: null plan");
+    if (op == 2) {
+        WgradPlanI W;
+        if (int e = wgs_check(wgs)) return e;
+        if (int e = wgrad_decide(gm, dtype, cfg, c_split, &W)) return e;
+        *out = csu_conv_plan{};
+        out->family = CSU_CONV_WGRAD;
+        out->n_problems = 1;
+        out->two_source = c_split;
+        out->cus = id_cus();
+        out->ksplit = 1;
+        out->wgrad_pick = W.pick;
+        out->wgrad_chunks = W.p.chunks;
+        out->wgrad_v2 = W.v2;
+        out->wgrad_rpc = W.p.rpc;
+        out->wgrad_last = W.total - (long)(W.p.chunks - 1) * W.p.rpc;
+        out->wgrad_ws_bytes = W.ws;
+        return 0;
+    }
+    ConvPlanI P;
+    if (int e = conv_decide(op, gm, dtype, cfg, wgs, c_split, nullptr, ws_bytes, &P)) return e;
+    conv_report(gm, P, out);
+    return 0;
 }
 
 extern "C" int csu_conv2d_wgrad_split_oihw(const csu_conv_geom* gm, int dtype, const void* x, const void* x2, int c_split,

@@ -105,6 +105,25 @@ class ConvGeom(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("B", "H", "W", "C", "OH", "OW", "N", "KH", "KW", "stride", "pad")]
 
 
+CONV_PLAN_PHASES = 16
+# csu_conv_family (include/csu.h)
+CONV_GEMM, CONV_IGEMM, CONV_IGEMM_DMA, CONV_HALO64, CONV_C16, CONV_C16D, CONV_WGRAD = range(7)
+
+
+class ConvPlan(ctypes.Structure):
+    """csu_conv_plan (include/csu.h)."""
+    _fields_ = ([(n, c_int32) for n in ("family", "n_problems", "two_source", "cus", "ksplit", "kper", "v2_bn", "v2_vw",
+                                        "gemm_vec", "wg_tiles_max", "wg_tiles_min", "wgs_idle")] +
+                [(n, c_int32 * CONV_PLAN_PHASES) for n in ("phase_family", "phase_cfg", "phase_bm", "phase_bn",
+                                                           "phase_ring")] +
+                [(n, ctypes.c_int64 * CONV_PLAN_PHASES) for n in ("phase_rows", "phase_tiles")] +
+                [(n, c_int32 * CONV_PLAN_PHASES) for n in ("phase_nk", "phase_grid", "phase_tiles_max", "phase_tiles_min",
+                                                           "phase_idle", "phase_xcd_rem")] +
+                [("wgrad_pick", c_int32), ("wgrad_chunks", c_int32), ("wgrad_v2", c_int32), ("_pad", c_int32),
+                 ("wgrad_rpc", ctypes.c_int64),
+                 ("wgrad_last", ctypes.c_int64), ("wgrad_ws_bytes", ctypes.c_uint64)])
+
+
 # name -> (restype, argtypes); mirrors include/csu.h
 _SIGS = {
     "csu_last_error_string": (ctypes.c_char_p, []),
@@ -354,6 +373,11 @@ _SIGS = {
                                         c_size_t, c_void_p]),
     "csu_conv2d_wgrad_oihw": (ctypes.c_int, [ctypes.POINTER(ConvGeom), ctypes.c_int, c_void_p, c_void_p, ctypes.c_int,
                                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "csu_conv2d_plan": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ConvGeom), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, c_size_t, ctypes.POINTER(ConvPlan)]),
+    "csu_conv2d_ex2": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ConvGeom), ctypes.c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, c_size_t,
+                                      c_void_p]),
 }
 
 _lib = None

@@ -3242,6 +3242,19 @@ def _conv_geom(B, H, W, C, N, KH, KW, stride, pad):
     return g
 
 
+def conv_plan(op: int, g, dtype: torch.dtype, cfg: int = -1, wgs: int = 0, c_split: int = 0,
+              ws_bytes: Optional[int] = None) -> "_lib.ConvPlan":
+    """csu_conv2d_plan: the launch plan of a convolution with geometry g (op 0 forward, 1 input
+    gradient, 2 weight gradient) -- the function the launches take every decision from.  ws_bytes
+    None: the workspace conv2d itself passes (csu_conv2d_workspace); no GPU needed."""
+    dt = dtype_code_of(dtype)
+    if ws_bytes is None:
+        ws_bytes = lib().csu_conv2d_workspace(op, ctypes.byref(g), dt) if op in (0, 1) and not c_split else 0
+    plan = _lib.ConvPlan()
+    check(lib().csu_conv2d_plan(op, ctypes.byref(g), dt, cfg, wgs, c_split, ws_bytes, ctypes.byref(plan)), "conv2d_plan")
+    return plan
+
+
 def _conv_wgrad(g, x, dy, dt, c_real=None, out=None):
     """fp32 (dW, db) of the forward conv with geometry g: dW in torch's (N, c_real, KH, KW) layout,
     written so by the kernel's final reduction (input channels >= c_real, the zero padding of a

@@ -775,8 +775,10 @@ int csu_conv2d_dgrad(const csu_conv_geom* g, int dtype, const void* dy, const vo
  * implicit GEMM; 1 + k: the persistent LDS-DMA kernel (bf16, gathered channels % 64 == 0) in tile
  * configuration k (0: 128x128 3-stage, 1: 256x128 2-stage 8 waves, 2: 256x128 3-stage 8 waves,
  * 3: 128x64 4-stage, 4: 256x64 3-stage 8 waves, 5: 128x64 3-stage, 6 / 7: 256x256 8 waves, 8:
- * 512x64 8 waves); 20: the halo kernel of 3x3 stride-1 pad-1 convs with 64 gathered and 64 output
- * channels (H % 2 == 0, W % 64 == 0); CSU_E_ARG when not eligible. */
+ * 512x64 8 waves, 9: 64x64 4-stage, 10: 128x64 3-stage, 11: 64x128 3-stage, the last three two
+ * workgroups per CU); 20: the halo kernel of 3x3 stride-1 pad-1 convs with 64 gathered and 64 output
+ * channels (H % 2 == 0, W % 64 == 0); 21: the 16 -> 144 channel 3x3 stride-1 pad-1 kernel and its input
+ * gradient (W % 64 == 0); CSU_E_ARG when not eligible. */
 int csu_conv2d_ex(int op, const csu_conv_geom* g, int dtype, const void* src, const void* w, const float* bias, void* out,
                   int cfg, void* stream);
 /* The plain operators with a workspace (op 0: csu_conv2d_fwd, 1: csu_conv2d_dgrad): one-problem bf16
@@ -822,6 +824,80 @@ int csu_conv2d_wgrad_split_oihw(const csu_conv_geom* g, int dtype, const void* x
                                 float* dw_db, void* workspace, size_t ws_bytes, void* stream);
 int csu_conv2d_wgrad_ex(const csu_conv_geom* g, int dtype, const void* x, const void* dy, int c_real, float* dw_db,
                         void* workspace, size_t ws_bytes, int cfg, void* stream);
+
+/* The launch plan of a convolution call: which kernel csu_conv2d_fwd / _dgrad / _wgrad and their
+ * _ws / _ex / _split forms run for (op, geometry, dtype, cfg, wgs, c_split, ws_bytes) and how the
+ * persistent kernels divide their tiles.  Host only: it touches the device for the CU count alone
+ * (256 without a GPU).  It is the function the launches themselves take every decision from, so the
+ * report cannot differ from what is launched. */
+enum csu_conv_family {
+    CSU_CONV_GEMM = 0,        /* conv_gemm: scalar-gather tiles (fp32, or bf16 with channels % 4 != 0) */
+    CSU_CONV_IGEMM = 1,       /* igemm_bf16: register-staged v2 implicit GEMM, one tile per workgroup */
+    CSU_CONV_IGEMM_DMA = 2,   /* igemm_dma: persistent LDS-DMA implicit GEMM */
+    CSU_CONV_HALO64 = 3,      /* conv3_halo64 */
+    CSU_CONV_C16 = 4,         /* conv3_c16 */
+    CSU_CONV_C16D = 5,        /* conv3_c16d */
+    CSU_CONV_WGRAD = 6        /* op 2: the weight-gradient kernel named by wgrad_pick */
+};
+enum csu_conv_wgrad_v2 {      /* the kernel behind wgrad_pick -1 */
+    CSU_WGRAD_V2_NONE = 0,        /* wgrad_pick >= 0 */
+    CSU_WGRAD_V2_BF16 = 1,        /* conv_wgrad_bf16<false>: C % 8 == 0, N % 8 == 0, operands below 2 GiB */
+    CSU_WGRAD_V2_BF16_N4 = 2,     /* conv_wgrad_bf16<true>: N % 4 == 0 */
+    CSU_WGRAD_V2_BF16_WIDE = 3,   /* conv_wgrad_kernel<bf16, vector gathers>: 64-bit offsets or N % 4 != 0 */
+    CSU_WGRAD_V2_BF16_SCALAR = 4, /* conv_wgrad_kernel<bf16, scalar gathers>: C % 8 != 0 */
+    CSU_WGRAD_V2_F32 = 5,         /* conv_wgrad_kernel<float, vector gathers> */
+    CSU_WGRAD_V2_F32_SCALAR = 6   /* conv_wgrad_kernel<float, scalar gathers> */
+};
+#define CSU_CONV_PLAN_PHASES 16
+typedef struct {
+    int32_t family;           /* csu_conv_family of the first problem (every problem's: phase_family) */
+    int32_t n_problems;       /* problems launched: 1, or the non-empty stride phases of an input gradient;
+                               * the per-phase arrays report the first CSU_CONV_PLAN_PHASES of them */
+    int32_t two_source;       /* c_split (two sources / two destinations), else 0 */
+    int32_t cus;              /* CU count the heuristics used (rounded up to a multiple of 8) */
+    int32_t ksplit, kper;     /* K parts of the v2 launch (1: none) and gathered columns per part */
+    int32_t v2_bn, v2_vw;     /* IGEMM: output columns per tile (32 narrow / 64) and gather vector width; else 0 */
+    int32_t gemm_vec;         /* GEMM: 1 = the 8-channel vector gathers */
+    /* the largest and smallest tile (item) count of any workgroup over all problems, and the
+     * workgroups that get none */
+    int32_t wg_tiles_max, wg_tiles_min, wgs_idle;
+    int32_t phase_family[CSU_CONV_PLAN_PHASES];
+    int32_t phase_cfg[CSU_CONV_PLAN_PHASES];      /* the csu_conv2d_ex cfg that forces this choice: 0 v2, 1 + k, 20,
+                                                   * 21; -1 for GEMM */
+    int32_t phase_bm[CSU_CONV_PLAN_PHASES];       /* tile rows and columns (HALO64: 128 x 64, C16 / C16D: 64 x N) */
+    int32_t phase_bn[CSU_CONV_PLAN_PHASES];
+    int32_t phase_ring[CSU_CONV_PLAN_PHASES];     /* ring stages S of the persistent kernels, else 0 */
+    int64_t phase_rows[CSU_CONV_PLAN_PHASES];     /* GEMM rows M */
+    int64_t phase_tiles[CSU_CONV_PLAN_PHASES];    /* tiles or items */
+    int32_t phase_nk[CSU_CONV_PLAN_PHASES];       /* K slices per tile (HALO64 / C16 / C16D: 1) */
+    int32_t phase_grid[CSU_CONV_PLAN_PHASES];     /* workgroups launched for the problem */
+    int32_t phase_tiles_max[CSU_CONV_PLAN_PHASES];
+    int32_t phase_tiles_min[CSU_CONV_PLAN_PHASES];
+    int32_t phase_idle[CSU_CONV_PLAN_PHASES];
+    int32_t phase_xcd_rem[CSU_CONV_PLAN_PHASES];  /* tiles % 8 of the persistent kernels, else 0 */
+    /* op 2 */
+    int32_t wgrad_pick;       /* -1 the v2 kernels, else the configuration k of csu_conv2d_wgrad_ex's cfg 1 + k */
+    int32_t wgrad_chunks;     /* row (halo: segment) chunks, one partial slab each */
+    int32_t wgrad_v2;         /* csu_conv_wgrad_v2 */
+    int32_t _pad;
+    int64_t wgrad_rpc;        /* rows (halo: 64-pixel segments) per chunk */
+    int64_t wgrad_last;       /* rows (segments) of the last chunk */
+    uint64_t wgrad_ws_bytes;  /* workspace the call needs */
+} csu_conv_plan;
+/* op 0 forward, 1 input gradient, 2 weight gradient.  cfg as csu_conv2d_ex (op 0 / 1) or
+ * csu_conv2d_wgrad_ex (op 2).  wgs: 0, or the persistent grid (csu_conv2d_ex2).  c_split: 0, or the
+ * two-source split.  ws_bytes: workspace of a _ws call (0: none).  Runs the same validation as the
+ * launches; 0 or a csu_status. */
+int csu_conv2d_plan(int op, const csu_conv_geom* g, int dtype, int cfg, int wgs, int c_split, size_t ws_bytes,
+                    csu_conv_plan* out);
+/* csu_conv2d_ex with every choice explicit (tests, tuning).  second / c_split: NULL / 0, or the
+ * two-source form (op 0: second = x2, op 1: second = dx2; needs csu_conv2d_split_ok).  wgs: 0 = the
+ * grid the plain entries launch (1 or 2 workgroups per CU); otherwise the number of persistent
+ * workgroups of igemm_dma, conv3_halo64, conv3_c16 and conv3_c16d, a positive multiple of 8 (the
+ * kernels give each of the 8 XCDs gridDim.x / 8 workgroups) of at most 65536, else CSU_E_ARG; the
+ * one-tile-per-workgroup kernels ignore it.  workspace / ws_bytes as the _ws entries (NULL / 0: none). */
+int csu_conv2d_ex2(int op, const csu_conv_geom* g, int dtype, const void* src, const void* w, const float* bias, void* out,
+                   void* second, int c_split, int cfg, int wgs, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Step glue (csrc/glue.hip), the elementwise passes between the kernels above:

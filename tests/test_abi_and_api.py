@@ -50,6 +50,9 @@ def test_struct_layout_matches_header(tmp_path):
               "csu_gemm_desc": (_lib.GemmDesc, ["M", "a", "b_trans", "bias", "out", "ldc", "cfg"]),
               "csu_mlp_dropout": (_lib.MlpDropout, ["rng", "site_out", "p", "row_scale", "rows_per_sample"]),
               "csu_conv_geom": (_lib.ConvGeom, ["B", "KH", "pad"]),
+              "csu_conv_plan": (_lib.ConvPlan, ["family", "ksplit", "wgs_idle", "phase_family", "phase_ring", "phase_rows",
+                                                "phase_tiles", "phase_nk", "phase_xcd_rem", "wgrad_pick", "wgrad_v2", "wgrad_rpc",
+                                                "wgrad_ws_bytes"]),
               "csu_wslab_item": (_lib.WslabItem, ["slab", "dst", "N", "tk", "chunks"]),
               "csu_wgrad_group_item": (_lib.WgradGroupItem, ["dy", "x", "dw_db", "slab", "M", "N", "K"]),
               "csu_ln_param_item": (_lib.LnParamItem, ["workspace", "dbeta", "rows", "C"])}

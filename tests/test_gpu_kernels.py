@@ -425,9 +425,13 @@ def test_gemm_vs_torch(M, N, K, b_trans, mode):
 
 
 @pytest.mark.parametrize("cfg", [0, 1, 2, 3, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19])
-@pytest.mark.parametrize("M,N,K", [(1000, 64, 64), (4099, 192, 128), (300, 520, 1024), (16384, 1024, 256)])
+@pytest.mark.parametrize("M,N,K", [(1000, 64, 64), (4099, 192, 128), (300, 520, 1024), (16384, 1024, 256),
+                                   (16500, 840, 128)])
 def test_gemm_tile_configs_and_gelu_out(M, N, K, cfg):
-    """Every tile configuration of the b[n][k] kernel, with the dual (h, gelu(h)) epilogue."""
+    """Every tile configuration of the b[n][k] kernel, with the dual (h, gelu(h)) epilogue.  The persistent gemm4
+    configurations (cfg 10-19) give a workgroup no second tile at the first three shapes and the same 2 to 8 tiles
+    to every workgroup at the fourth; at (16500, 840, 128) they own 1..2 to 7..8 tiles: unequal counts, tiles % 8 != 0,
+    partial last M and N tiles (the gemm4 table)."""
     from csu import ops
     d = dev()
     g = torch.Generator(device=d).manual_seed(M + N + K + cfg)
