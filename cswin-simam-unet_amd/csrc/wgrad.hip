@@ -12,13 +12,22 @@
 // staged row-major ([token][column], XOR-swizzled 16-B chunks) through TWO LDS buffers with a
 // two-step register prefetch (branch-free buffer loads), fragments gathered with the transposing
 // ds_read_b64_tr_b16.  Measured (tools/wgrad_timing.py, tools/wgrad_bench.py): a step is bound by
-// the per-CU load rate (L2 hits ~70 GB/s/CU, the compulsory HBM part slower), not by latency
-// (deeper prefetch, more workgroups per CU: no change) nor the MFMAs.  The chunk partials go to
+// the per-CU load rate, not by latency (deeper prefetch, more workgroups per CU: no change) nor the
+// MFMAs.  That rate was ~70 GB/s/CU for one Linear alone with its operands in L2; in the step's grouped
+// launches, beside every other CU's loads, a 256 x 128 workgroup stages its 48 KB per 64-token step in
+// 1.2-1.4 us = 35-40 GB/s per CU (profiles/wg01_wgrad_timeline.txt; DESIGN.md §6 has 22-30 GB/s for the
+// 4-wave tiles), and a CU without a workgroup stages nothing: see the group planner below.  The chunk partials go to
 // tile-local slabs reduced by ONE coalesced pass in chunk order (wslab_reduce): an in-launch
 // combine (arrival counters, agent-scope release/acquire) measured 1.3-4x slower per launch.
 // fp32 path: 64x64 tiles, v_mfma_f32_32x32x2f32, [chunk][N*K + N] slabs + csu_colsum.
+#include <algorithm>
 #include <cstdlib>
+#include <functional>
+#include <map>
+#include <mutex>
+#include <queue>
 #include <type_traits>
+#include <vector>
 
 #include "common.hpp"
 
@@ -33,9 +42,15 @@ __device__ unsigned long long wg_ts[4][16384];
 #define WG_STAMP(k) do { if (threadIdx.x < 1 && blockIdx.x < 16384) wg_ts[k][blockIdx.x + threadIdx.x] = __builtin_amdgcn_s_memrealtime(); } while (0)
 __device__ unsigned long long wg_steps[4][64];   // core-clock stamps of the phases of the first 64 steps of block 0
 #define STEP_STAMP(k, i) do { if (blockIdx.x == 0 && threadIdx.x < 1 && (i) < 64) wg_steps[k][(i) + threadIdx.x] = __builtin_amdgcn_s_memtime(); } while (0)
+// where the workgroup ran: XCC_ID (hardware register 20, bits 3:0) << 16 | HW_ID (register 4) bits 15:0
+// (wave, SIMD, pipe, CU, SH, SE) -- tools/wgrad_group_timeline.py groups the stamps by XCD and CU
+__device__ unsigned wg_hw[16384];
+#define WG_WHERE() do { if (threadIdx.x < 1 && blockIdx.x < 16384) wg_hw[blockIdx.x + threadIdx.x] = \
+    (__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 16) | (__builtin_amdgcn_s_getreg(4 | (15 << 11)) & 0xffffu); } while (0)
 #else
 #define WG_STAMP(k) do {} while (0)
 #define STEP_STAMP(k, i) do {} while (0)
+#define WG_WHERE() do {} while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -370,15 +385,22 @@ struct WgGroup {
     int count;
 };
 
+// workgroups resident per CU of wgrad_group<tn, tk>: its launch bound, and what the group planner's
+// dispatch model counts as slots (the 256 x 128 tile runs 8 waves, NTH = 2 NT)
+constexpr int group_wg_per_cu(int tn, int tk) { return tn > 128 || tn * tk > 256 * 128 ? 1 : 2; }
+
 template <int TN, int TK, int NTH = NT, int D = 2>
-__global__ __launch_bounds__(NTH, NTH > NT || TN * TK > 256 * 128 ? 1 : 2) void wgrad_group(WgGroup g) {
+__global__ __launch_bounds__(NTH, NTH > NT ? 1 : group_wg_per_cu(TN, TK)) void wgrad_group(WgGroup g) {
     __shared__ __attribute__((aligned(16))) bf16 lds[2 * TileCfg<TN, TK, NTH>::BUF];
+    WG_STAMP(0);
+    WG_WHERE();
     const int lt = __builtin_amdgcn_readfirstlane((int)xcd_tile(blockIdx.x, gridDim.x));
     int i = 0;
     while (i + 1 < g.count && g.b0[i + 1] <= lt) ++i;
     i = __builtin_amdgcn_readfirstlane(i);
     wgrad_tile_body<TN, TK, D, NTH>(lds, lt - g.b0[i], g.M[i], g.N[i], g.K[i], g.rpc[i], g.chunks[i], g.dy[i], g.x[i],
                                     g.dst[i], g.slab[i]);
+    WG_STAMP(3);
 }
 
 // dst[n][k] = sum_c slab[tile(n, k)][c][n % TN][k % TK], then dst[N*K + n] = sum_c bslab[n / TN][c][n % TN].
@@ -673,25 +695,28 @@ extern "C" size_t csu_linear_wgrad_group_plan(long M, int N, int K, int* tn, int
     return ((size_t)nt * kt * a * b + (size_t)nt * a) * c * sizeof(float);
 }
 
+constexpr int kPass[5][2] = {{256, 128}, {128, 128}, {128, 64}, {64, 128}, {64, 64}};   // launch order of the tile shapes
+
+static int launch_group(int T, int TK, WgGroup& g, hipStream_t st) {
+    if (!g.count) return 0;
+    if (T == 256) wgrad_group<256, 128, 2 * NT><<<(unsigned)g.b0[g.count], 2 * NT, 0, st>>>(g);
+    else if (T == 128 && TK == 128) wgrad_group<128, 128><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
+    else if (T == 128) wgrad_group<128, 64><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
+    else if (TK == 128) wgrad_group<64, 128><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
+    else wgrad_group<64, 64><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
+    g.count = 0;
+    return check_launch("linear_wgrad_group");
+}
+
 extern "C" int csu_linear_wgrad_group(const csu_wgrad_group_item* items, int count, void* stream) {
     if (count < 0 || (count && !items)) return fail(CSU_E_ARG, "linear_wgrad_group: bad args");
     hipStream_t st = as_stream(stream);
-    constexpr int kPass[5][2] = {{256, 128}, {128, 128}, {128, 64}, {64, 128}, {64, 64}};
     for (int pass = 0; pass < 5; ++pass) {   // one launch per tile shape present
         const int T = kPass[pass][0], TK = kPass[pass][1];
         WgGroup g;
         g.count = 0;
         g.b0[0] = 0;
-        auto flush = [&]() -> int {
-            if (!g.count) return 0;
-            if (T == 256) wgrad_group<256, 128, 2 * NT><<<(unsigned)g.b0[g.count], 2 * NT, 0, st>>>(g);
-            else if (T == 128 && TK == 128) wgrad_group<128, 128><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
-            else if (T == 128) wgrad_group<128, 64><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
-            else if (TK == 128) wgrad_group<64, 128><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
-            else wgrad_group<64, 64><<<(unsigned)g.b0[g.count], NT, 0, st>>>(g);
-            g.count = 0;
-            return check_launch("linear_wgrad_group");
-        };
+        auto flush = [&]() -> int { return launch_group(T, TK, g, st); };
         for (int i = 0; i < count; ++i) {
             const csu_wgrad_group_item& it = items[i];
             if (it.M < 1 || it.N % 8 || it.K % 8 || !it.dy || !it.x || !it.dw_db)
@@ -716,6 +741,264 @@ extern "C" int csu_linear_wgrad_group(const csu_wgrad_group_item* items, int cou
         if (int e = flush()) return e;
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Group-aware plan: the token chunks of every Linear of a grouped launch chosen together, so that
+// the launch's workgroups come out as whole rounds over the CUs (group_plan above cuts each Linear
+// alone: stage 3's proj gets 4096-token workgroups beside the ~5500-token ones of qkv / fc1 / fc2).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// Modelled time of one workgroup of tile tn x tk: fixed + 64-token steps x step (us).  Calibration
+// (profiles/wg01_wgrad_timeline.txt, the per-Linear plan's launches of the 512 x 512 B16 step on 256
+// CUs): step = (median workgroup time - fixed) / steps of the median workgroup -- 256 x 128: 106.9 us
+// at 86 steps; 128 x 128: 90.4 us at ~50; 64 x 128: 21.1 us at 22; 64 x 64: 40.7 us at ~20 -- with the
+// ~3 us fixed part of model_us above (tools/wgrad_bench.py).  These are times beside the launch's
+// other workgroups (two per CU for the 4-wave tiles), which is how the model uses them.
+struct WgCost { double fixed_us, step_us; };
+constexpr WgCost wg_cost(int tn, int tk) {
+    return tn == 256 ? WgCost{3.0, 1.21} : tn * tk == 128 * 128 ? WgCost{3.0, 1.75} : tn * tk == 128 * 64 ? WgCost{3.0, 0.82}
+                                                                                                        : WgCost{3.0, 1.9};
+}
+constexpr double kHbmBytesPerUs = 4.0e6;   // slab writes + reads in the objective (~4 TB/s achieved)
+constexpr int kCapDiv = 8;                 // slab bytes <= operand bytes * 2 / 16 per Linear
+
+struct GItem {   // one Linear of a launch: shape, tile, and the chunking under evaluation
+    int idx;
+    long M;
+    int N, K, tiles, nt;
+    long maxc, c, rpc;
+};
+
+inline long slab_bytes_of(const GItem& it, int tn, int tk, long c) {
+    return c <= 1 ? 0 : ((long)it.tiles * tn * tk + (long)it.nt * tn) * c * 4;
+}
+
+inline void cut(GItem& it, long c) {   // c equal chunks, rows a multiple of TM
+    if (c > it.maxc) c = it.maxc;
+    if (c < 1) c = 1;
+    it.rpc = ((it.M + c - 1) / c + TM - 1) / TM * TM;
+    it.c = (it.M + it.rpc - 1) / it.rpc;
+}
+
+// Greedy dispatch of the launch's logical workgroups in order[]: XCD x walks its contiguous share of
+// the ids (xcd_tile) on (CUs per XCD) x (workgroups per CU) slots, each workgroup to the slot free first.
+double makespan_us(const std::vector<GItem>& its, const std::vector<int>& order, int tn, int tk, int cus) {
+    const WgCost wc = wg_cost(tn, tk);
+    std::vector<float> cost;
+    for (int o : order) {
+        const GItem& it = its[o];
+        for (long ch = 0; ch < it.c; ++ch) {
+            const long rows = std::min(it.rpc, it.M - ch * it.rpc);
+            const float t = (float)(wc.fixed_us + wc.step_us * (double)((rows + TM - 1) / TM));
+            cost.insert(cost.end(), (size_t)it.tiles, t);
+        }
+    }
+    const long W = (long)cost.size();
+    const int xcds = cus >= kXcds ? kXcds : cus;
+    const int slots = std::max(1, cus / xcds) * group_wg_per_cu(tn, tk);
+    const long q = W / kXcds, rem = W % kXcds;   // the kernel's xcd_tile always deals over 8
+    std::vector<double> end((size_t)xcds * slots, 0.0);   // fewer than 8 XCDs: shares x, x + xcds, .. in turn
+    double worst = 0.0;
+    for (int x = 0; x < kXcds; ++x) {
+        const long b = x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q, n = x < rem ? q + 1 : q;
+        double* e = end.data() + (size_t)(x % xcds) * slots;
+        std::priority_queue<double, std::vector<double>, std::greater<double>> pq(e, e + slots);
+        for (long w = b; w < b + n; ++w) {
+            const double t = pq.top() + cost[(size_t)w];
+            pq.pop();
+            pq.push(t);
+            if (t > worst) worst = t;
+        }
+        for (int s = 0; s < slots; ++s) { e[s] = pq.top(); pq.pop(); }
+    }
+    return worst;
+}
+
+struct LaunchPlan {
+    double us;
+    std::vector<GItem> its;     // with c / rpc chosen
+    std::vector<int> order;     // positions -> index into its
+};
+
+// One launch: search the common target chunk length, then the order (as given, or longest workgroups
+// first with the ragged / short ones last), by modelled time = makespan + slab bytes at the HBM rate.
+LaunchPlan plan_launch(std::vector<GItem> its, int tn, int tk, int cus) {
+    std::vector<long> targets;
+    for (const GItem& it : its)
+        for (long c = 1; c <= it.maxc; ++c) targets.push_back(((it.M + c - 1) / c + TM - 1) / TM * TM);
+    std::sort(targets.begin(), targets.end(), std::greater<long>());
+    targets.erase(std::unique(targets.begin(), targets.end()), targets.end());
+    if (targets.size() > 96) {   // bounded search: an even sample of the candidates
+        std::vector<long> s;
+        for (size_t i = 0; i < 96; ++i) s.push_back(targets[i * targets.size() / 96]);
+        targets.swap(s);
+    }
+    std::vector<int> asgiven(its.size());
+    for (size_t i = 0; i < its.size(); ++i) asgiven[i] = (int)i;
+    LaunchPlan best;
+    best.us = 1e300;
+    for (long T : targets) {   // longest target first: ties keep the fewer, longer chunks (smaller slabs)
+        long slab = 0;
+        for (GItem& it : its) {
+            cut(it, (long)((double)it.M / (double)T + 0.5));
+            slab += slab_bytes_of(it, tn, tk, it.c);
+        }
+        std::vector<int> sorted = asgiven;
+        std::stable_sort(sorted.begin(), sorted.end(), [&](int a, int b) { return its[a].rpc > its[b].rpc; });
+        const std::vector<int>* orders[2] = {&asgiven, &sorted};
+        for (int o = 0; o < 2; ++o) {
+            const double us = makespan_us(its, *orders[o], tn, tk, cus) + 2.0 * (double)slab / kHbmBytesPerUs;
+            if (us < best.us - 1e-9) {
+                best.us = us;
+                best.its = its;
+                best.order = *orders[o];
+            }
+        }
+    }
+    return best;
+}
+
+std::mutex g_plan_mu;
+std::map<std::vector<long>, std::vector<csu_wgrad_group_plan>> g_plan_cache;
+
+void plan_all(const std::vector<long>& key, int count, int cus, csu_wgrad_group_plan* out) {
+    int launch = 0;
+    for (int pass = 0; pass < 5; ++pass) {
+        const int T = kPass[pass][0], TK = kPass[pass][1];
+        std::vector<GItem> cls;
+        for (int i = 0; i < count; ++i) {
+            const long M = key[1 + 3 * i];
+            const int N = (int)key[2 + 3 * i], K = (int)key[3 + 3 * i];
+            int tn, tk, c;
+            long r;
+            group_plan(M, N, K, &tn, &tk, &c, &r);
+            if (tn != T || tk != TK) continue;
+            GItem it;
+            it.idx = i; it.M = M; it.N = N; it.K = K;
+            it.nt = (N + tn - 1) / tn;
+            it.tiles = it.nt * ((K + tk - 1) / tk);
+            const long per_chunk = ((long)it.tiles * tn * tk + (long)it.nt * tn) * 4;
+            it.maxc = std::min(std::max(M / 1024, 1L), std::max(M * (N + K) * 2 / kCapDiv / per_chunk, 1L));
+            it.c = 1; it.rpc = (M + TM - 1) / TM * TM;
+            cls.push_back(it);
+        }
+        const int n = (int)cls.size();
+        if (!n) continue;
+        // cut of the item list into ceil(n / WGG_MAX) launches: two launches search the cut, more split evenly
+        const int L = (n + WGG_MAX - 1) / WGG_MAX;
+        std::vector<LaunchPlan> best;
+        double best_us = 1e300;
+        auto eval = [&](const std::vector<int>& cuts) {   // cuts: L + 1 boundaries
+            std::vector<LaunchPlan> lp;
+            double us = 0.0;
+            for (int l = 0; l < L; ++l) {
+                lp.push_back(plan_launch(std::vector<GItem>(cls.begin() + cuts[l], cls.begin() + cuts[l + 1]), T, TK, cus));
+                us += lp.back().us;
+            }
+            if (us < best_us - 1e-9) { best_us = us; best.swap(lp); }
+        };
+        if (L == 2) {
+            for (int c = WGG_MAX; c >= n - WGG_MAX; --c) eval({0, c, n});
+        } else {
+            std::vector<int> cuts(L + 1);
+            for (int l = 0; l <= L; ++l) cuts[l] = (int)((long)n * l / L);
+            eval(cuts);
+        }
+        for (const LaunchPlan& lp : best) {
+            for (size_t p = 0; p < lp.order.size(); ++p) {
+                const GItem& it = lp.its[lp.order[p]];
+                csu_wgrad_group_plan& o = out[it.idx];
+                o.tn = T; o.tk = TK; o.chunks = (int)it.c; o.launch = launch; o.pos = (int)p; o._pad = 0;
+                o.rpc = it.rpc;
+                o.slab_bytes = (uint64_t)slab_bytes_of(it, T, TK, it.c);
+            }
+            ++launch;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int csu_linear_wgrad_group_plan_all(const csu_wgrad_group_item* items, int count, int cus,
+                                               csu_wgrad_group_plan* out) {
+    if (count < 0 || cus < 0 || (count && (!items || !out))) return fail(CSU_E_ARG, "linear_wgrad_group_plan_all: bad args");
+    if (!cus) cus = num_cus();
+    std::vector<long> key(1 + 3 * (size_t)count);
+    key[0] = cus;
+    for (int i = 0; i < count; ++i) {
+        const csu_wgrad_group_item& it = items[i];
+        if (it.M < 1 || it.M > 0x7fffffffL || it.N < 8 || it.K < 8 || it.N % 8 || it.K % 8)
+            return fail(CSU_E_ARG, "linear_wgrad_group_plan_all: bad item");
+        key[1 + 3 * i] = it.M; key[2 + 3 * i] = it.N; key[3 + 3 * i] = it.K;
+    }
+    // the plan depends on (cus, shapes in order) alone: remember it (an eager step plans the same lists every step)
+    std::lock_guard<std::mutex> lock(g_plan_mu);
+    auto f = g_plan_cache.find(key);
+    if (f == g_plan_cache.end()) {
+        if (g_plan_cache.size() >= 64) g_plan_cache.clear();
+        std::vector<csu_wgrad_group_plan> p((size_t)count);
+        plan_all(key, count, cus, p.data());
+        f = g_plan_cache.emplace(key, std::move(p)).first;
+    }
+    std::copy(f->second.begin(), f->second.end(), out);
+    return 0;
+}
+
+extern "C" void csu_linear_wgrad_group_model(int tn, int tk, double* fixed_us, double* step_us, int* wg_per_cu) {
+    if (fixed_us) *fixed_us = wg_cost(tn, tk).fixed_us;
+    if (step_us) *step_us = wg_cost(tn, tk).step_us;
+    if (wg_per_cu) *wg_per_cu = group_wg_per_cu(tn, tk);
+}
+
+extern "C" int csu_linear_wgrad_group_planned(const csu_wgrad_group_item* items, const csu_wgrad_group_plan* plans,
+                                              int count, void* stream) {
+    if (count < 0 || (count && (!items || !plans))) return fail(CSU_E_ARG, "linear_wgrad_group_planned: bad args");
+    hipStream_t st = as_stream(stream);
+    std::vector<int> ord((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const csu_wgrad_group_item& it = items[i];
+        const csu_wgrad_group_plan& p = plans[i];
+        if (it.M < 1 || it.M > 0x7fffffffL || it.N < 8 || it.K < 8 || it.N % 8 || it.K % 8 || !it.dy || !it.x || !it.dw_db)
+            return fail(CSU_E_ARG, "linear_wgrad_group_planned: bad item");
+        int tn, tk, c;
+        long r;
+        group_plan(it.M, it.N, it.K, &tn, &tk, &c, &r);
+        if (p.tn != tn || p.tk != tk || p.rpc < TM || p.rpc % TM || p.rpc > 0x7fffffc0L || p.chunks < 1 ||
+            (long)p.chunks != (it.M + p.rpc - 1) / p.rpc || p.launch < 0 || p.pos < 0)
+            return fail(CSU_E_ARG, "linear_wgrad_group_planned: bad plan");
+        if (p.chunks > 1 && !it.slab) return fail(CSU_E_WORKSPACE, "linear_wgrad_group_planned: item needs a slab workspace");
+        ord[i] = i;
+    }
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+        return plans[a].launch != plans[b].launch ? plans[a].launch < plans[b].launch : plans[a].pos < plans[b].pos;
+    });
+    WgGroup g;
+    g.count = 0;
+    g.b0[0] = 0;
+    int T = 0, TK = 0, cur = -1;
+    for (int j = 0; j < count; ++j) {
+        const csu_wgrad_group_item& it = items[ord[j]];
+        const csu_wgrad_group_plan& p = plans[ord[j]];
+        const long wgs = (long)((it.N + p.tn - 1) / p.tn) * ((it.K + p.tk - 1) / p.tk) * p.chunks;
+        if (p.launch != cur) {
+            if (int e = launch_group(T, TK, g, st)) return e;
+            cur = p.launch; T = p.tn; TK = p.tk;
+        } else if (p.tn != T || p.tk != TK || g.count == WGG_MAX || (long)g.b0[g.count] + wgs > (1L << 30)) {
+            return fail(CSU_E_ARG, "linear_wgrad_group_planned: a launch holds one tile shape, <= 48 items, < 2^30 workgroups");
+        }
+        if (wgs > (1L << 30)) return fail(CSU_E_ARG, "linear_wgrad_group_planned: too many workgroups");
+        const int k = g.count;
+        g.dy[k] = (const bf16*)it.dy;
+        g.x[k] = (const bf16*)it.x;
+        g.dst[k] = it.dw_db;
+        g.slab[k] = it.slab;
+        g.M[k] = (int)it.M; g.N[k] = it.N; g.K[k] = it.K; g.chunks[k] = p.chunks; g.rpc[k] = (int)p.rpc;
+        g.b0[k + 1] = g.b0[k] + (int)wgs;
+        g.count = k + 1;
+    }
+    return launch_group(T, TK, g, st);
 }
 
 extern "C" int csu_wslab_reduce_batch(const csu_wslab_item* items, int count, void* stream) {
@@ -752,5 +1035,8 @@ extern "C" int csu_debug_wgrad_ts(unsigned long long* host) {
 }
 extern "C" int csu_debug_wgrad_steps(unsigned long long* host) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(csu::wg_steps), sizeof(csu::wg_steps), 0, hipMemcpyDeviceToHost);
+}
+extern "C" int csu_debug_wgrad_hw(unsigned* host) {
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(csu::wg_hw), sizeof(csu::wg_hw), 0, hipMemcpyDeviceToHost);
 }
 #endif

@@ -67,6 +67,12 @@ class WgradGroupItem(ctypes.Structure):
                 ("N", c_int32), ("K", c_int32)]
 
 
+class WgradGroupPlan(ctypes.Structure):
+    """csu_wgrad_group_plan (include/csu.h)."""
+    _fields_ = [("tn", c_int32), ("tk", c_int32), ("chunks", c_int32), ("launch", c_int32), ("pos", c_int32),
+                ("_pad", c_int32), ("rpc", ctypes.c_int64), ("slab_bytes", ctypes.c_uint64)]
+
+
 class LepeReduceItem(ctypes.Structure):
     """csu_lepe_reduce_item (include/csu.h)."""
     _fields_ = [("part", c_void_p), ("dw", c_void_p * 2), ("db", c_void_p * 2), ("nblk", c_int32), ("channels", c_int32),
@@ -249,6 +255,10 @@ _SIGS = {
     "csu_linear_wgrad_group_plan": (c_size_t, [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "csu_linear_wgrad_group": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
+    "csu_linear_wgrad_group_plan_all": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "csu_linear_wgrad_group_planned": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, c_void_p]),
+    "csu_linear_wgrad_group_model": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
     "csu_augment_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
     "csu_augment_draw": (ctypes.c_int, [ctypes.POINTER(AugmentConfig)] + [ctypes.c_int] * 3 + [c_void_p, ctypes.c_uint,

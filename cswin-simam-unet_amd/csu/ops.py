@@ -465,6 +465,9 @@ def _ln_param_grads(ctx, rows, C, work, nblk):
 # then.  DEFER_WGRAD = False (tests): one launch (+ reduction) per Linear, inline.
 DEFER_WGRAD = True
 GROUP_WGRAD = True   # False (tests): deferred slab sums only
+# The grouped launches' token chunks planned over the whole list (csu_linear_wgrad_group_plan_all) instead of
+# per Linear; CSU_WGRAD_BALANCE=0: per Linear.  Default per profiles/wg01_wgrad_balance_ab.txt.
+BALANCE_WGRAD = os.environ.get("CSU_WGRAD_BALANCE", "1") != "0"
 _WG_PENDING: list = []   # (WslabItem, out, workspace): reductions of tile kernels already launched
 _WG_DEFER: list = []     # (dy2, x2, out): whole weight gradients deferred to the grouped launch
 _WG_POST: list = []      # callables run after the deferred weight gradients are complete
@@ -476,12 +479,21 @@ def _wgrad_flush():
         L = lib()
         dev = defer[0][0].device
         gitems = (_lib.WgradGroupItem * len(defer))()
+        plans = None
+        if BALANCE_WGRAD:   # the chunks of the whole list planned together (whole workgroup rounds per launch)
+            plans = (_lib.WgradGroupPlan * len(defer))()
+            for i, (dy2, x2, _) in enumerate(defer):
+                gitems[i].M, gitems[i].N, gitems[i].K = dy2.shape[0], dy2.shape[1], x2.shape[1]
+            check(L.csu_linear_wgrad_group_plan_all(gitems, len(defer), 0, plans), "linear_wgrad_group_plan_all")
         keep, flops, nbytes = [], 0, 0
         for i, (dy2, x2, out) in enumerate(defer):
             M, N = dy2.shape
             K = x2.shape[1]
             tn, tk, ch = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            nws = L.csu_linear_wgrad_group_plan(M, N, K, ctypes.byref(tn), ctypes.byref(tk), ctypes.byref(ch))
+            if plans is not None:
+                nws, tn.value, tk.value, ch.value = plans[i].slab_bytes, plans[i].tn, plans[i].tk, plans[i].chunks
+            else:
+                nws = L.csu_linear_wgrad_group_plan(M, N, K, ctypes.byref(tn), ctypes.byref(tk), ctypes.byref(ch))
             slab = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None
             keep.append(slab)
             it = gitems[i]
@@ -494,7 +506,11 @@ def _wgrad_flush():
                 _WG_PENDING.append((w, out, slab))
             flops += 2 * M * N * K
             nbytes += M * (N + K) * 2 + (N * K + N) * 4
-        _launch("linear_wgrad", lambda: L.csu_linear_wgrad_group(gitems, len(defer), stream_ptr(dev)), flops, nbytes)
+        if plans is not None:
+            _launch("linear_wgrad", lambda: L.csu_linear_wgrad_group_planned(gitems, plans, len(defer), stream_ptr(dev)),
+                    flops, nbytes)
+        else:
+            _launch("linear_wgrad", lambda: L.csu_linear_wgrad_group(gitems, len(defer), stream_ptr(dev)), flops, nbytes)
     pend, _WG_PENDING[:] = list(_WG_PENDING), []
     if not pend:
         _wgrad_post()

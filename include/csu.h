@@ -337,6 +337,27 @@ typedef struct {
 } csu_wgrad_group_item;
 size_t csu_linear_wgrad_group_plan(long M, int N, int K, int* tn, int* tk, int* chunks);
 int csu_linear_wgrad_group(const csu_wgrad_group_item* items, int count, void* stream);
+/* The same launches planned over the whole list: one common target chunk length per launch, so
+ * that the workgroups of a launch fill whole rounds of the CUs (csu_linear_wgrad_group_plan cuts
+ * each Linear alone).  plan_all reads M, N, K and the order of the items only (never the
+ * pointers); cus = 0 asks the device, cus > 0 makes no GPU call.  The plan is a function of
+ * (cus, shapes in order) alone.  Per item: the tile (csu_linear_wgrad_group_plan's), the token
+ * chunks, rows per chunk (a multiple of 64; the last chunk may be shorter), the slab workspace the
+ * item needs (0: dw_db is written directly; <= operand bytes / 8), the launch it goes to (launches
+ * run in ascending order, <= 48 items each, one tile shape) and its position in that launch.
+ * csu_linear_wgrad_group_planned launches items with such plans (slab: plan's slab_bytes); items
+ * with chunks > 1 are completed by csu_wslab_reduce_batch as above.  csu_linear_wgrad_group_model:
+ * the constants of the dispatch model the plan minimises (us per workgroup = fixed + 64-token steps
+ * x step; workgroups resident per CU). */
+typedef struct {
+    int32_t tn, tk, chunks, launch, pos, _pad;
+    int64_t rpc;
+    uint64_t slab_bytes;
+} csu_wgrad_group_plan;
+int csu_linear_wgrad_group_plan_all(const csu_wgrad_group_item* items, int count, int cus, csu_wgrad_group_plan* out);
+int csu_linear_wgrad_group_planned(const csu_wgrad_group_item* items, const csu_wgrad_group_plan* plans, int count,
+                                   void* stream);
+void csu_linear_wgrad_group_model(int tn, int tk, double* fixed_us, double* step_us, int* wg_per_cu);
 /* Same with the plan forced (tuning / tests): bf16 output tile tn x tk (64 or 128; 0 = auto) and
  * the number of token chunks (0 = auto).  The fp32 path ignores them. */
 size_t csu_linear_wgrad_tuned_workspace(long M, int N, int K, int tn, int tk, int chunks);
