@@ -83,6 +83,28 @@ template <int G> __device__ __forceinline__ float strided_sum(const float* __res
     for (; j < n; j += G) s0 += p[j];
     return (s0 + s1) + (s2 + s3);
 }
+// inclusive integer scan of v over a workgroup of NT threads (all of them call it); total = the sum over all of
+// them.  wsum: NT / 64 words of LDS, free again on return
+template <int NT> __device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* wsum, unsigned& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned y = __shfl_up(inc, o, 64);
+        inc += lane >= o ? y : 0u;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    unsigned before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < NT / 64; ++k) {
+        before += k < w ? wsum[k] : 0u;
+        total += wsum[k];
+    }
+    __syncthreads();
+    return inc + before;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -104,6 +104,20 @@ struct HdArgs {
 };
 constexpr float HD_DEAD = -1.f;
 
+// The Lovasz-Softmax term (csu_seg_lovasz_*): for the classes of mask (C), in the order of their bits m = 0 .. |C|-1,
+// the forward leaves every pixel's key and value in keys / vals (|C|, B, HW) for csu_sort_pairs:
+//   e = fminf(t == c ? sum_{k != c} p_k : p_c, 1) (a NaN counts as 1),  key = 0x3F800000 - bits(e), in [0, 0x3F800000]:
+//   ascending keys are descending e; a dead pixel has e = 0 and bit 30 set, which puts it behind every live one;
+//   value = (fg << 31) | the pixel's flat index in its segment (b HW + pix, or pix with per_image).
+// The backward reads the planes psi (|C|, B, HW) through BdArgs (phi = psi, w_bd = w_lv, bg = mask): load_phi<LV>.
+struct LvArgs {
+    unsigned* keys;
+    unsigned* vals;
+    unsigned mask;
+    int per_image;
+};
+constexpr unsigned LV_ONE = 0x3F800000u, LV_DEAD = 1u << 30;
+
 // u^gamma; 1 when gamma = 0, also at u = 0.  gamma is uniform: the usual exponents 1 and 2 skip powf, which
 // measured 75 us of the 200 us of forward + backward at B 16, K 5, 512 x 512 (profiles/hard_example_loss_timing.txt)
 __device__ __forceinline__ float hd_pow(float u, float gamma) {
@@ -159,15 +173,17 @@ template <typename T, int KB> constexpr int cl_vec() { return KB * (int)sizeof(T
 
 // f[j][k] = phi of pixel e0 + j and class k for the classes that carry the term, else 0; only pixels inside
 // [lo, hi) are read.  A unit that is whole and whose plane address is on a vector boundary takes one V-wide load.
-template <int KB, int V>
+// LV: the planes are psi (|C|, B, HW) of the Lovasz term, class k's plane the one of its place among the bits of bd.bg
+template <int KB, int V, bool LV = false>
 __device__ __forceinline__ void load_phi(const CeArgs& a, const BdArgs& bd, long b, long e0, long lo, long hi, bool full,
                                          float (&f)[V][KB]) {
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
 #pragma unroll
         for (int j = 0; j < V; ++j) f[j][k] = 0.f;
-        if (k < a.K && (bd.bg || k > 0)) {
-            const float* q = bd.phi + (b * a.K + k) * a.HW + e0;
+        if (k < a.K && (LV ? (((unsigned)bd.bg >> k) & 1u) != 0 : (bd.bg || k > 0))) {
+            const long plane = LV ? (long)__popc((unsigned)bd.bg & ((1u << k) - 1u)) * a.B + b : b * a.K + k;
+            const float* q = bd.phi + plane * a.HW + e0;
             if (V > 1 && full && ((uintptr_t)q % (V * sizeof(float))) == 0) {
                 float v[V];
                 loadv<V>(q, v);
@@ -274,8 +290,10 @@ __device__ __forceinline__ void item_range(const CeArgs& a, long it, bool vec_ok
 
 // BD: one more sum per item, the boundary term's sum of p_c phi_c, at index 2 + 5 K
 // HD: the CE numerator is the sum of l = w[t] u^gamma L, and with hd.keys every pixel's l goes there as its key
-template <typename T, int KB, int MODE, bool BD, bool HD>
-__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, HdArgs hd, int vec_ok, float* __restrict__ partial) {
+// LV: every pixel's Lovasz key and value go to lv.keys / lv.vals for the classes of lv.mask; the sums are unchanged
+template <typename T, int KB, int MODE, bool BD, bool HD, bool LV = false>
+__global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, HdArgs hd, int vec_ok, float* __restrict__ partial,
+                                                 LvArgs lv = LvArgs{nullptr, nullptr, 0u, 0}) {
     constexpr int V = ce_vec(KB, MODE);
     constexpr bool LANE_CNT = KB >= 16;
     constexpr int NC = LANE_CNT ? 1 : KB;
@@ -331,6 +349,25 @@ __global__ __launch_bounds__(NT) void ce_partial(CeArgs a, BdArgs bd, HdArgs hd,
                     if (hd.keys && e0 + j >= lo && e0 + j < hi) hd.keys[b * a.HW + e0 + j] = t >= 0 ? l : HD_DEAD;
                 } else {
                     ce += live ? wt * ((logf(s) + m) - zt) : 0.f;
+                }
+                if constexpr (LV) {
+                    const long pix = e0 + j;
+                    if (pix >= lo && pix < hi) {
+                        float u = 0.f;   // the foreground error, formed as the hard-example term forms its u
+#pragma unroll
+                        for (int k = 0; k < KB; ++k) u += t == k ? 0.f : z[j][k];
+                        const unsigned flat = (unsigned)(lv.per_image ? pix : b * a.HW + pix);
+#pragma unroll
+                        for (int k = 0; k < KB; ++k) {
+                            if (k < K && ((lv.mask >> k) & 1u)) {
+                                const bool fg = t == k;
+                                const float e = fminf(fg ? u : z[j][k], 1.f);
+                                const long at = ((long)__popc(lv.mask & ((1u << k) - 1u)) * a.B + b) * a.HW + pix;
+                                lv.keys[at] = live ? LV_ONE - __float_as_uint(e) : LV_DEAD | LV_ONE;
+                                lv.vals[at] = (fg ? 0x80000000u : 0u) | flat;
+                            }
+                        }
+                    }
                 }
                 sw += wt;
                 const int pred = live ? arg : -1;
@@ -543,10 +580,13 @@ __global__ __launch_bounds__(NT) void ce_finish(int B, int K, int cpi, int rows,
 // HD: the CE part of dz_k becomes g w_ce m w[t] (p_k - [k = t]) (u^gamma + gamma q u^(gamma - 1) L) / W.  m comes from
 // the pixel's stored key against tau, never from l formed again here: this kernel's l need not round as the
 // forward's did, and a key that moved across tau would move the gradient by a whole pixel's worth.
-template <typename T, int KB, int MODE, bool BD, bool HD>
+// LV (csu_seg_lovasz_bwd, with BD): the planes are the forward's psi, which carry their own scale (the coefficient
+// behind 1 / sum w is 1), f = psi on the classes of the mask in bd.bg; the same gated pair.
+template <typename T, int KB, int MODE, bool BD, bool HD, bool LV = false>
 __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, HdArgs hd, int vec_ok, int rows,
                                                   const float* __restrict__ dloss, const float* __restrict__ coef, float w_ce,
                                                   float tv_scale, T* __restrict__ dz) {
+    static_assert(!LV || BD, "the Lovasz term takes the boundary term's place in the expression");
     constexpr int V = ce_vec(KB, MODE);
     const int K = a.K;
     if (bd.w_bd != nullptr) {
@@ -583,7 +623,7 @@ __global__ __launch_bounds__(NT) void ce_backward(CeArgs a, BdArgs bd, HdArgs hd
             float z[V][KB];
             load_unit<T, KB, MODE, V>(a, zb, e0, lo, hi, full, z);
             float f[BD ? V : 1][BD ? KB : 1];
-            if constexpr (BD) load_phi<KB, V>(a, bd, b, e0, lo, hi, e0 >= lo && e0 + V <= hi, f);
+            if constexpr (BD) load_phi<KB, V, LV>(a, bd, b, e0, lo, hi, e0 >= lo && e0 + V <= hi, f);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 bool live;
@@ -778,11 +818,12 @@ struct HdSelect {
 
 // the two forward launches and the backward launch, shared by csu_seg_ce_* (BD = false), csu_seg_bd_* and
 // csu_seg_hard_* (HD; with keys the selection and its sums run between the two)
-template <bool BD, bool HD = false>
+// LV: csu_seg_lovasz_fwd's first two launches; the sort and the term's own kernels follow them there
+template <bool BD, bool HD = false, bool LV = false>
 int ce_forward(const char* what, const CeArgs& a, const BdArgs& bd, int rows, int dtype, int pad_ok, float w_ce, float w_tv,
                float alpha, float beta, float smooth, int include_background, float* terms, float* loss, double* stats,
                float* coef, void* workspace, void* stream, const HdArgs& hd = HdArgs{0.f, nullptr, nullptr, nullptr},
-               const HdSelect& hs = HdSelect{nullptr, nullptr, nullptr, 0}) {
+               const HdSelect& hs = HdSelect{nullptr, nullptr, nullptr, 0}, const LvArgs& lv = LvArgs{nullptr, nullptr, 0u, 0}) {
     const int K = a.K, KB = ce_bucket(K);
     const int nb = (int)(a.items < CE_BLOCKS ? a.items : CE_BLOCKS);
     hipStream_t st = as_stream(stream);
@@ -793,8 +834,8 @@ int ce_forward(const char* what, const CeArgs& a, const BdArgs& bd, int rows, in
         using T = std::conditional_t<decltype(f32)::value, float, bf16>;
         with_bucket(KB, [&](auto kb) {
             with_mode(mode, [&](auto md) {
-                ce_partial<T, decltype(kb)::value, decltype(md)::value, BD, HD>
-                    <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, (float*)workspace);
+                ce_partial<T, decltype(kb)::value, decltype(md)::value, BD, HD, LV>
+                    <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, (float*)workspace, lv);
             });
         });
     });
@@ -813,7 +854,7 @@ int ce_forward(const char* what, const CeArgs& a, const BdArgs& bd, int rows, in
     return check_launch(what);
 }
 
-template <bool BD, bool HD = false>
+template <bool BD, bool HD = false, bool LV = false>
 int ce_backward_launch(const char* what, const CeArgs& a, const BdArgs& bd, int rows, int dtype, int pad_ok, float w_ce,
                        float w_tv, int include_background, const float* dloss, const float* coef, void* dz, void* stream,
                        const HdArgs& hd = HdArgs{0.f, nullptr, nullptr, nullptr}) {
@@ -831,7 +872,7 @@ int ce_backward_launch(const char* what, const CeArgs& a, const BdArgs& bd, int 
                 if constexpr (BD)   // the gated pair: see ce_backward
                     ce_backward<T, decltype(kb)::value, decltype(md)::value, false, false>
                         <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
-                ce_backward<T, decltype(kb)::value, decltype(md)::value, BD, HD>
+                ce_backward<T, decltype(kb)::value, decltype(md)::value, BD, HD, LV>
                     <<<nb, NT, 0, st>>>(a, bd, hd, vec_ok, rows, dloss, coef, w_ce, tv_scale, (T*)dz);
             });
         });
@@ -966,4 +1007,239 @@ extern "C" int csu_seg_hard_bwd(int B, int K, long HW, int rows, int dtype, cons
     return ce_backward_launch<false, true>("seg_hard_bwd", a, BdArgs{nullptr, nullptr, 0}, rows, dtype, pad_ok, w_ce, w_tversky,
                                            include_background, dloss, coef, dz, stream,
                                            HdArgs{gamma, const_cast<float*>(keys), nullptr, nullptr});
+}
+
+// ---- the same loss with the Lovasz-Softmax term: + w_lv[0] LS --------------------------------------
+// After ce_partial<LV> has left the keys and values and csu_sort_pairs has put every segment in descending e:
+//   lv_count   the foreground pixels of every tile of LT sorted pairs -> cnt[segment][tile]
+//   lv_scan    one workgroup per segment: the exclusive scan of its row of cnt in place, G[segment] = the total
+//   lv_coef    per tile: the scan within the tile on top of the tile's prefix gives F of every pair; from the integers
+//              I = G - F, U = I + (j - 1) the increment g in fp64, psi = -/+ g scale rounded once to fp32 and stored
+//              at the pair's pixel, and the tile's sum of e g in fp64 (a thread's 8 pairs in order, then a fixed
+//              tree) -> lsum[segment][tile].  A dead pair (bit 30 of the key) gets psi = 0 and adds nothing.
+//   lv_finish  one workgroup: LS = sum over segments of scale (sum over tiles of lsum), in a fixed order; terms,
+//              loss[0] += w_lv[0] LS on top of ce_finish's, and the 1 behind 1 / sum w in coef.
+namespace csu {
+namespace {
+
+constexpr int LV_EPT = 8;
+constexpr int LT = NT * LV_EPT;   // 2048 pairs per tile
+constexpr int LV_BLOCKS = 1 << 18;
+
+struct LvPlan {
+    long len, ntl, items, segs;   // a segment's pairs, its tiles, segs * ntl
+    int B, nc, per_image, present_only;
+};
+
+LvPlan lv_plan(int B, long HW, unsigned mask, int per_image, int present_only) {
+    LvPlan p;
+    p.B = B;
+    p.nc = __builtin_popcount(mask);
+    p.per_image = per_image != 0;
+    p.present_only = present_only != 0;
+    p.segs = p.per_image ? (long)p.nc * B : p.nc;
+    p.len = p.per_image ? HW : (long)B * HW;
+    p.ntl = (p.len + LT - 1) / LT;
+    p.items = p.segs * p.ntl;
+    return p;
+}
+
+// scale of a segment: [it counts] / (number counted x (B if per_image else 1)); counted within the segment's image
+__device__ __forceinline__ double lv_scale(const LvPlan& p, const unsigned* __restrict__ G, long seg) {
+    const long b = p.per_image ? seg % p.B : 0, stride = p.per_image ? p.B : 1;
+    int present = 0;
+    for (int m = 0; m < p.nc; ++m) present += G[m * stride + b] > 0u ? 1 : 0;
+    const int counted = p.present_only ? present : p.nc;
+    const bool on = !p.present_only || G[seg] > 0u;
+    return on ? 1.0 / ((double)(counted > 1 ? counted : 1) * (double)(p.per_image ? p.B : 1)) : 0.0;
+}
+
+__global__ __launch_bounds__(NT) void lv_count(const unsigned* __restrict__ vals, LvPlan p, unsigned* __restrict__ cnt) {
+    __shared__ unsigned wsum[NT / 64];
+    for (long it = blockIdx.x; it < p.items; it += gridDim.x) {
+        const long seg = it / p.ntl, tile = it - seg * p.ntl, first = tile * LT;
+        const int n = (int)min((long)LT, p.len - first);
+        const unsigned* v = vals + seg * p.len + first;
+        unsigned c = 0;
+        for (int i = threadIdx.x; i < n; i += NT) c += v[i] >> 31;
+        unsigned total;
+        block_scan<NT>(c, wsum, total);
+        if (threadIdx.x == 0) cnt[it] = total;
+    }
+}
+
+__global__ __launch_bounds__(NT) void lv_scan(unsigned* __restrict__ cnt, unsigned* __restrict__ G, LvPlan p) {
+    __shared__ unsigned wsum[NT / 64];
+    for (long seg = blockIdx.x; seg < p.segs; seg += gridDim.x) {
+        unsigned* row = cnt + seg * p.ntl;
+        unsigned carry = 0;
+        for (long c0 = 0; c0 < p.ntl; c0 += NT) {
+            const long i = c0 + threadIdx.x;
+            const unsigned v = i < p.ntl ? row[i] : 0u;
+            unsigned total;
+            const unsigned inc = block_scan<NT>(v, wsum, total);
+            if (i < p.ntl) row[i] = carry + inc - v;
+            carry += total;
+        }
+        if (threadIdx.x == 0) G[seg] = carry;
+    }
+}
+
+__global__ __launch_bounds__(NT) void lv_coef(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, LvPlan p,
+                                              const unsigned* __restrict__ cnt, const unsigned* __restrict__ G,
+                                              float* __restrict__ psi, double* __restrict__ lsum) {
+    __shared__ unsigned wsum[NT / 64];
+    __shared__ double red[NT / 64];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long it = blockIdx.x; it < p.items; it += gridDim.x) {
+        const long seg = it / p.ntl, tile = it - seg * p.ntl, first = tile * LT;
+        const int n = (int)min((long)LT, p.len - first);
+        const unsigned* k = keys + seg * p.len + first;
+        const unsigned* v = vals + seg * p.len + first;
+        float* out = psi + seg * p.len;
+        const double scale = lv_scale(p, G, seg);
+        const long Gs = G[seg];
+        unsigned key[LV_EPT], val[LV_EPT], mine = 0;
+        const int i0 = threadIdx.x * LV_EPT;
+#pragma unroll
+        for (int r = 0; r < LV_EPT; ++r) {
+            const bool valid = i0 + r < n;
+            key[r] = valid ? k[i0 + r] : LV_DEAD;
+            val[r] = valid ? v[i0 + r] : 0u;
+            mine += val[r] >> 31;
+        }
+        unsigned total;
+        long F = (long)cnt[it] + (block_scan<NT>(mine, wsum, total) - mine);   // the foreground pairs before this thread's
+        double acc = 0.0;
+#pragma unroll
+        for (int r = 0; r < LV_EPT; ++r) {
+            const bool fg = (val[r] >> 31) != 0, live = (key[r] & LV_DEAD) == 0;
+            const long I = Gs - F, U = I + (first + i0 + r);   // j - 1 = the pair's place in the segment
+            const double g = fg ? 1.0 / (double)U : U == 0 ? 1.0 : (double)I / ((double)U * (double)(U + 1));
+            const float e = __uint_as_float(LV_ONE - key[r]);
+            acc += live ? (double)e * g : 0.0;
+            const long at = val[r] & 0x7FFFFFFFu;
+            if (i0 + r < n && at < p.len) out[at] = live ? (float)((fg ? -g : g) * scale) : 0.f;
+            F += fg ? 1 : 0;
+        }
+        acc = wave_sum_d(acc);
+        if (lane == 0) red[wv] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) lsum[it] = (red[0] + red[1]) + (red[2] + red[3]);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(NT) void lv_finish(const double* __restrict__ lsum, const unsigned* __restrict__ G, LvPlan p,
+                                                const float* __restrict__ w_lv, float* __restrict__ loss,
+                                                float* __restrict__ terms, float* __restrict__ coef_one) {
+    __shared__ double red[NT / 64];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double ls = 0.0;
+    for (long seg = wv; seg < p.segs; seg += NT / 64) {
+        double s = 0.0;
+        for (long i = lane; i < p.ntl; i += 64) s += lsum[seg * p.ntl + i];
+        ls += wave_sum_d(s) * lv_scale(p, G, seg);
+    }
+    if (lane == 0) red[wv] = ls;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double LS = (red[0] + red[1]) + (red[2] + red[3]);
+        const float base = loss[0];
+        terms[0] = base;
+        terms[1] = (float)LS;
+        loss[0] = (float)((double)base + (double)w_lv[0] * LS);
+        coef_one[0] = 1.f;
+    }
+}
+
+// workspace: the (2 + 5 K) partial sums per item, the tile sums (fp64), the sort's scratch pairs and workspace, the
+// tile counts and the segment totals
+struct LvLayout {
+    size_t partial, lsum, kalt, valt, sort, sort_bytes, cnt, G, total;
+};
+LvLayout lv_layout(int B, int K, long HW, const LvPlan& p) {
+    LvLayout l;
+    const size_t N = (size_t)p.nc * B * HW;
+    l.partial = 0;
+    l.lsum = ((size_t)ce_plan(B, HW).items * ce_nsum(K) * sizeof(float) + 7) & ~(size_t)7;
+    l.kalt = l.lsum + (size_t)p.items * sizeof(double);
+    l.valt = l.kalt + N * sizeof(unsigned);
+    l.sort = l.valt + N * sizeof(unsigned);
+    l.sort_bytes = csu_sort_pairs_workspace((int)p.segs, p.len);
+    l.cnt = l.sort + l.sort_bytes;
+    l.G = l.cnt + (size_t)p.items * sizeof(unsigned);
+    l.total = (l.G + (size_t)p.segs * sizeof(unsigned) + 7) & ~(size_t)7;
+    return l;
+}
+
+bool lv_mask_ok(int B, int K, long HW, unsigned mask) {
+    if (mask == 0 || (K < 32 && (mask >> K) != 0)) return false;
+    return (long)__builtin_popcount(mask) * B * HW < (1L << 31);
+}
+
+}  // namespace
+}  // namespace csu
+
+extern "C" size_t csu_seg_lovasz_workspace(int B, int K, long HW, uint32_t class_mask, int per_image) {
+    if (B < 1 || HW < 1 || K < 2 || K > KMAX || HW >= (1L << 31) || !lv_mask_ok(B, K, HW, class_mask)) return 0;
+    return lv_layout(B, K, HW, lv_plan(B, HW, class_mask, per_image, 0)).total;
+}
+
+extern "C" int csu_seg_lovasz_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                                  int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                                  float w_ce, float w_tversky, float alpha, float beta, float smooth, int include_background,
+                                  uint32_t class_mask, int present_only, int per_image, const float* w_lv,
+                                  uint32_t* sorted_keys, uint32_t* sorted_vals, float* psi, float* loss, float* terms,
+                                  double* stats, float* coef, void* workspace, size_t ws_bytes, void* stream) {
+    if (int e = ce_args("seg_lovasz_fwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky, true)) return e;
+    if (!(alpha >= 0.f) || !(beta >= 0.f)) return fail(CSU_E_ARG, "seg_lovasz_fwd: alpha and beta must be >= 0");
+    if (!(smooth > 0.f)) return fail(CSU_E_ARG, "seg_lovasz_fwd: smooth must be > 0");
+    if (HW >= (1L << 31) || !lv_mask_ok(B, K, HW, class_mask))
+        return fail(CSU_E_ARG, "seg_lovasz_fwd: class_mask needs a bit, none at or above K, and |C| B HW < 2^31");
+    if (!z || !t || !loss || !coef || !terms) return fail(CSU_E_ARG, "seg_lovasz_fwd: null z, t, loss, terms or coef");
+    if (!w_lv || !sorted_keys || !sorted_vals || !psi)
+        return fail(CSU_E_ARG, "seg_lovasz_fwd: null w_lv, sorted_keys, sorted_vals or psi");
+    if (((uintptr_t)sorted_keys | (uintptr_t)sorted_vals | (uintptr_t)psi) & 3)
+        return fail(CSU_E_ARG, "seg_lovasz_fwd: sorted_keys, sorted_vals or psi misaligned");
+    if (!workspace || ((uintptr_t)workspace & 7) || ws_bytes < csu_seg_lovasz_workspace(B, K, HW, class_mask, per_image))
+        return fail(CSU_E_WORKSPACE, "seg_lovasz_fwd: workspace (8-byte aligned)");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    const LvPlan p = lv_plan(B, HW, class_mask, per_image, present_only);
+    const LvLayout l = lv_layout(B, K, HW, p);
+    char* ws = (char*)workspace;
+    if (int e = ce_forward<false, false, true>("seg_lovasz_fwd", a, BdArgs{nullptr, nullptr, 0}, rows, dtype, pad_ok, w_ce,
+                                               w_tversky, alpha, beta, smooth, include_background, nullptr, loss, stats, coef,
+                                               ws + l.partial, stream, HdArgs{0.f, nullptr, nullptr, nullptr},
+                                               HdSelect{nullptr, nullptr, nullptr, 0},
+                                               LvArgs{sorted_keys, sorted_vals, class_mask, p.per_image}))
+        return e;
+    if (int e = csu_sort_pairs((int)p.segs, p.len, 31, sorted_keys, sorted_vals, (uint32_t*)(ws + l.kalt),
+                               (uint32_t*)(ws + l.valt), ws + l.sort, l.sort_bytes, stream))
+        return e;
+    hipStream_t st = as_stream(stream);
+    const int nb = (int)(p.items < LV_BLOCKS ? p.items : LV_BLOCKS);
+    const int nsb = (int)(p.segs < LV_BLOCKS ? p.segs : LV_BLOCKS);
+    unsigned* cnt = (unsigned*)(ws + l.cnt);
+    unsigned* G = (unsigned*)(ws + l.G);
+    double* lsum = (double*)(ws + l.lsum);
+    lv_count<<<nb, NT, 0, st>>>(sorted_vals, p, cnt);
+    lv_scan<<<nsb, NT, 0, st>>>(cnt, G, p);
+    lv_coef<<<nb, NT, 0, st>>>(sorted_keys, sorted_vals, p, cnt, G, psi, lsum);
+    lv_finish<<<1, NT, 0, st>>>(lsum, G, p, w_lv, loss, terms, coef + 2 * (long)rows * K + 1);
+    return check_launch("seg_lovasz_fwd");
+}
+
+extern "C" int csu_seg_lovasz_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                                  int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                                  const float* dloss, const float* coef, float w_ce, float w_tversky, int include_background,
+                                  uint32_t class_mask, const float* psi, const float* w_lv, void* dz, void* stream) {
+    if (int e = ce_args("seg_lovasz_bwd", B, K, HW, rows, dtype, s_b, s_k, s_pix, label_dtype, w_ce, w_tversky, true)) return e;
+    if (HW >= (1L << 31) || !lv_mask_ok(B, K, HW, class_mask))
+        return fail(CSU_E_ARG, "seg_lovasz_bwd: class_mask needs a bit, none at or above K, and |C| B HW < 2^31");
+    if (!z || !t || !dloss || !coef || !dz) return fail(CSU_E_ARG, "seg_lovasz_bwd: null z, t, dloss, coef or dz");
+    if (!psi || !w_lv) return fail(CSU_E_ARG, "seg_lovasz_bwd: null psi or w_lv");
+    const CeArgs a = ce_pack(B, K, HW, z, s_b, s_k, s_pix, label_dtype, t, ignore_index, class_weight);
+    return ce_backward_launch<true, false, true>("seg_lovasz_bwd", a, BdArgs{psi, w_lv, (int)class_mask}, rows, dtype, pad_ok,
+                                                 w_ce, w_tversky, include_background, dloss, coef, dz, stream);
 }

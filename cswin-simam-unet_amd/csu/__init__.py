@@ -13,7 +13,8 @@ from .train import (bce_loss, dice_coefficient, evaluate_model, iou_score, make_
                     train_model, train_step)
 from .losses import (BoundarySegLoss, MultiClassSegLoss, SegLoss, bce_dice_loss, boundary_loss, ce_dice_boundary_loss,
                      ce_dice_loss, ce_loss, dice_loss, linear_ramp, multiclass_dice_loss, tversky_loss,
-                     HardExampleSegLoss, dice_focal_loss, dice_topk_loss, focal_loss, topk_ce_loss)
+                     HardExampleSegLoss, dice_focal_loss, dice_topk_loss, focal_loss, topk_ce_loss,
+                     LovaszSegLoss, ce_lovasz_loss, lovasz_softmax_loss, reference_lovasz_softmax)
 from .optim import FusedAdam, FusedAdamW
 from .ema import WeightEMA
 from .infer import (SlidingWindowPredictor, evaluate_full_res, plan_axis, plan_tiles, reference_predict, window_1d)
@@ -38,4 +39,5 @@ __all__ = ["UNet", "DoubleConv", "Down", "Up", "CARAFE", "CARAFE4", "CSWinBlock"
            "reference_connected_components", "reference_postprocess_labels", "SpatialAugment", "reference_augment",
            "BoundarySegLoss", "boundary_loss", "ce_dice_boundary_loss", "linear_ramp", "signed_distance_map",
            "reference_signed_distance_map", "HardExampleSegLoss", "focal_loss", "dice_focal_loss", "topk_ce_loss",
-           "dice_topk_loss", "PatchPool", "PatchSampler", "PatchLoader", "reference_patch_sample"]
+           "dice_topk_loss", "PatchPool", "PatchSampler", "PatchLoader", "reference_patch_sample",
+           "LovaszSegLoss", "lovasz_softmax_loss", "ce_lovasz_loss", "reference_lovasz_softmax"]

@@ -338,6 +338,18 @@ _SIGS = {
     "csu_seg_hard_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p]
                          + [ctypes.c_long] * 3 + [ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_long, c_void_p]
                          + [c_void_p, c_void_p, c_float, c_float, ctypes.c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "csu_sort_pairs_workspace": (c_size_t, [ctypes.c_int, ctypes.c_long]),
+    "csu_sort_pairs": (ctypes.c_int, [ctypes.c_int, ctypes.c_long, ctypes.c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "csu_sort_pairs_tile": (ctypes.c_int, []),
+    "csu_seg_lovasz_workspace": (c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_uint32, ctypes.c_int]),
+    "csu_seg_lovasz_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p]
+                           + [ctypes.c_long] * 3 + [ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_long, c_void_p]
+                           + [c_float] * 5 + [ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int] + [c_void_p] * 9
+                           + [c_size_t, c_void_p]),
+    "csu_seg_lovasz_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_void_p]
+                           + [ctypes.c_long] * 3 + [ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_long, c_void_p]
+                           + [c_void_p, c_void_p, c_float, c_float, ctypes.c_int, ctypes.c_uint32, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
     "csu_pack_nhwc_bf16": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p,
                                           c_void_p, c_void_p]),
     "csu_stripe_lepe_wgrad": (ctypes.c_int, [ctypes.POINTER(StripeArgs), ctypes.c_int, c_void_p, c_void_p, c_void_p, c_size_t,

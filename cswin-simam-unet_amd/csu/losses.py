@@ -1,7 +1,8 @@
 """Training criteria beyond nn.BCELoss: soft Dice, BCE + Dice, Tversky (binary, ``SegLoss``) and softmax
 cross-entropy + per-class Dice / Tversky on integer label maps (``MultiClassSegLoss``), that with the boundary
 loss of signed distance maps on top (``BoundarySegLoss``), and that with a focal or top-k cross-entropy in the
-place of the plain one (``HardExampleSegLoss``, at the end).
+place of the plain one (``HardExampleSegLoss``), or with the Lovasz-Softmax surrogate of the IoU on top
+(``LovaszSegLoss``, at the end).
 
 One family, ``SegLoss``:  ``bce * BCE + tversky * mean_r(1 - TI_r)`` on probabilities ``p`` and
 targets ``t`` viewed as rows (one row for the whole batch, or one per image), with
@@ -631,3 +632,180 @@ def dice_topk_loss(num_classes: int, top_k: float = 0.1, ce: float = 1.0, dice: 
     return HardExampleSegLoss(num_classes, ce=ce, tversky=dice, alpha=0.5, beta=0.5, smooth=smooth / 2,
                               class_weight=class_weight, ignore_index=ignore_index, per_sample=per_sample,
                               include_background=include_background, top_k=top_k, schedule=schedule)
+
+
+def _lovasz_torch(z, t, classes, present_only: bool, per_image: bool, ignore_index: int):
+    """The Lovasz-Softmax term LS in torch ops, in z's floating dtype: z (B, K, *), t (B, *) int64, classes a sorted
+    list of class indices.  The order is ``torch.sort(descending=True, stable=True)`` of the clamped errors with the
+    dead pixels behind the live ones; the increments g are formed in fp64 from the integer counts and are constants
+    of the gradient, so autograd gives dLS/dp_c = -/+ g_rank scale."""
+    B, K = z.shape[0], z.shape[1]
+    z2, t2 = z.reshape(B, K, -1), t.reshape(B, -1)
+    live = t2 != ignore_index
+    p = torch.softmax(z2, 1)
+    cls = torch.as_tensor(classes, dtype=torch.int64, device=z.device)
+    fg = (t2.unsqueeze(0) == cls.view(-1, 1, 1)) & live.unsqueeze(0)                     # (|C|, B, HW)
+    off = 1.0 - torch.eye(K, dtype=z.dtype, device=z.device)[:, cls]
+    others = torch.einsum("bkn,kc->cbn", p, off)                                         # sum_{k != c} p_k, no 1 - p_c
+    e = torch.where(fg, others, p[:, cls].permute(1, 0, 2))
+    e = e + (torch.where(e < 1, e, torch.ones_like(e)) - e).detach()                     # fminf(e, 1); the gradient is e's
+    rows = len(classes) * B if per_image else len(classes)
+    e, fg, lv = e.reshape(rows, -1), fg.reshape(rows, -1), live.unsqueeze(0).expand_as(fg).reshape(rows, -1)
+    key = torch.where(lv, e.detach(), torch.full_like(e, -1.0))
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    es, fs, ls = e.gather(1, order), fg.gather(1, order).long(), lv.gather(1, order)
+    G = fs.sum(1, keepdim=True)
+    I = G - (fs.cumsum(1) - fs)
+    U = I + torch.arange(es.shape[1], device=z.device).view(1, -1)
+    Id, Ud = I.double(), U.double()
+    safe = torch.where(U > 0, Ud, torch.ones_like(Ud))
+    g = torch.where(fs > 0, 1.0 / safe, torch.where(U > 0, Id / (safe * (safe + 1.0)), torch.ones_like(Ud)))
+    g = torch.where(ls, g, torch.zeros_like(g))
+    present = (G.view(len(classes), -1) > 0)                                            # (|C|, B or 1)
+    counted = present if present_only else torch.ones_like(present)
+    number = counted.sum(0, keepdim=True).clamp(min=1).double() * (B if per_image else 1)
+    scale = (counted.double() / number).reshape(rows, 1)
+    return (es * (g * scale).to(z.dtype)).sum()
+
+
+def _lovasz_classes(classes, K: int, what: str):
+    """(sorted class list, present_only) of the ``classes`` argument."""
+    if isinstance(classes, str):
+        if classes not in ("present", "all"):
+            raise ValueError(f"{what}: classes is 'present', 'all' or a list of class indices (got {classes!r})")
+        return list(range(K)), classes == "present"
+    try:
+        cls = [c for c in classes]
+    except TypeError:
+        raise ValueError(f"{what}: classes is 'present', 'all' or a list of class indices (got {classes!r})") from None
+    if not cls or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < K for c in cls) or len(set(cls)) != len(cls):
+        raise ValueError(f"{what}: classes must be distinct class indices in [0, {K}) (got {classes!r})")
+    return sorted(cls), False
+
+
+def reference_lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, classes="present", per_image: bool = False,
+                             ignore_index: int = -100) -> torch.Tensor:
+    """The Lovasz-Softmax term of ``LovaszSegLoss`` in fp64 torch ops on the tensors' device: the statement of its
+    definition (differentiable in the logits).  logits (B, K, *spatial), target (B, *spatial) integer labels."""
+    cls, present_only = _lovasz_classes(classes, logits.shape[1], "reference_lovasz_softmax")
+    return _lovasz_torch(logits.double(), target.long(), cls, present_only, bool(per_image), int(ignore_index))
+
+
+class LovaszSegLoss(MultiClassSegLoss):
+    """``MultiClassSegLoss`` plus the Lovasz-Softmax loss of Berman, Triki and Blaschko ("The Lovasz-Softmax loss: a
+    tractable surrogate for the optimization of the intersection-over-union measure in neural networks", CVPR 2018),
+    the convex surrogate of the mean IoU that csu.train reports.  A segment is one class c of ``classes`` over the
+    whole batch, or one (image, class) pair with ``per_image``.  For a segment with n live pixels (label not
+    ``ignore_index``) in ascending flat index, p = softmax(z):
+
+        fg_i = [t_i = c],   e_i = min(sum_{k != c} p_k if fg_i else p_c, 1),
+        pi = the order of descending e, ties in ascending index,   G = sum fg,
+        for j = 1 .. n:  F = #fg among pi(1 .. j-1),  I = G - F,  U = I + (j - 1),
+        g_j = 1 / U if pi(j) is foreground, else I / (U (U + 1))            (g_1 = 1 when U = 0: G = 0),
+        LS_seg = sum_j e_pi(j) g_j,
+
+    the g_j being the increments of the Jaccard loss along the order (Berman's ``lovasz_grad``) in closed form.
+    ``classes="present"`` (the default) averages LS_seg over the classes with a foreground pixel (0 when there is
+    none), ``"all"`` or a list of class indices over all of them; with ``per_image`` that average is taken within
+    every image and LS is the mean over the B images.
+
+        loss = ce * CE + tversky * mean_r mean_{c in C} (1 - TI_rc) + lovasz_weight * LS.
+
+    ``ce = tversky = 0`` is legal here (the term alone).  The weight lives in a one-element device tensor the kernels
+    read: ``set_lovasz_weight(w)`` fills it in place, so a captured graph follows a schedule without a re-capture;
+    ``lovasz_weight`` is the host copy.  ``schedule``: a callable epoch -> weight, applied by ``on_epoch(epoch)``,
+    which csu.train.train_model calls at the start of every epoch.  ``last_terms``: the (2,) device tensor (loss
+    without the term, LS) of the last call.
+
+    On the GPU with K <= 32 the loss and its gradient come from the fused csu_seg_lovasz kernels and the stable
+    radix sort csu_sort_pairs, with no host synchronisation; CPU tensors and more classes take the same formula in
+    torch ops with ``torch.sort(stable=True)``."""
+
+    _other_terms = True
+
+    def __init__(self, num_classes: int, ce: float = 1.0, tversky: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
+                 smooth: float = 0.5, class_weight=None, ignore_index: int = -100, per_sample: bool = False,
+                 include_background: bool = True, lovasz: float = 1.0, classes="present", per_image: bool = False,
+                 schedule=None):
+        super().__init__(num_classes, ce, tversky, alpha, beta, smooth, class_weight, ignore_index, per_sample,
+                         include_background)
+        self._check_weight(lovasz)
+        self._classes, self.present_only = _lovasz_classes(classes, num_classes, "LovaszSegLoss")
+        if schedule is not None and not callable(schedule):
+            raise ValueError("LovaszSegLoss: schedule is a callable epoch -> weight, or None")
+        self.classes = classes if isinstance(classes, str) else list(self._classes)
+        self.per_image, self.schedule = bool(per_image), schedule
+        self._w, self._wlv = float(lovasz), {}
+        self.last_terms = None
+
+    @staticmethod
+    def _check_weight(w):
+        if isinstance(w, bool) or not float(w) >= 0.0 or float(w) == float("inf"):
+            raise ValueError(f"LovaszSegLoss: the Lovasz weight must be a finite number >= 0 (got {w!r})")
+
+    def __repr__(self):
+        return (f"LovaszSegLoss({super().__repr__()[len('MultiClassSegLoss('):-1]}, lovasz={self._w}, "
+                f"classes={self.classes!r}, per_image={self.per_image}, schedule={self.schedule!r})")
+
+    @property
+    def lovasz_weight(self) -> float:
+        """The current weight of the Lovasz-Softmax term (the host copy of the device scalar)."""
+        return self._w
+
+    def set_lovasz_weight(self, w: float) -> None:
+        """Set the weight; every device's scalar is filled in place (no re-capture, no synchronisation)."""
+        self._check_weight(w)
+        self._w = float(w)
+        for t in self._wlv.values():
+            t.fill_(self._w)
+
+    def on_epoch(self, epoch: int) -> None:
+        """Apply the schedule, if there is one, for the epoch that starts (0-based)."""
+        if self.schedule is not None:
+            self.set_lovasz_weight(self.schedule(int(epoch)))
+
+    def _scalar(self, device):
+        t = self._wlv.get(device)
+        if t is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LovaszSegLoss: call the criterion once on this device before capturing it in a "
+                                   "graph (the weight's device scalar is made at the first call)")
+            t = self._wlv[device] = torch.full((1,), self._w, dtype=torch.float32, device=device)
+        return t
+
+    def _run(self, logits, target, with_stats):
+        K = self.num_classes
+        target = self._label_map(logits, target)
+        with torch.autocast(logits.device.type, enabled=False):
+            w = self._scalar(logits.device)
+            if logits.is_cuda and K <= 32:
+                from . import ops
+                z = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
+                rows = logits.shape[0] if self.per_sample else 1
+                res = ops.seg_lovasz(z, target, w, self.params, self._classes, self.present_only, self.per_image,
+                                     self._weight(logits.device), self.ignore_index, rows, self.include_background,
+                                     with_stats)
+                self.last_terms = res[1]
+                return (res[0], res[2]) if with_stats else res[0]
+            z, t = logits.float(), target.long()
+            base = self._torch(z, t)
+            ls = _lovasz_torch(z, t, self._classes, self.present_only, self.per_image, self.ignore_index)
+            self.last_terms = torch.stack([base.detach(), ls.detach()])
+            loss = base + w[0] * ls
+            if not with_stats:
+                return loss
+            return loss, self.hard_stats(z.detach(), t)
+
+
+def lovasz_softmax_loss(num_classes: int, classes="present", per_image: bool = False, ignore_index: int = -100,
+                        schedule=None) -> LovaszSegLoss:
+    """The Lovasz-Softmax term alone (weight 1), with the per-class metrics of MultiClassSegLoss."""
+    return LovaszSegLoss(num_classes, ce=0.0, tversky=0.0, ignore_index=ignore_index, lovasz=1.0, classes=classes,
+                         per_image=per_image, schedule=schedule)
+
+
+def ce_lovasz_loss(num_classes: int, ce: float = 1.0, lovasz: float = 1.0, classes="present", per_image: bool = False,
+                   class_weight=None, ignore_index: int = -100, schedule=None) -> LovaszSegLoss:
+    """ce * CE + lovasz * Lovasz-Softmax (Berman's recommended pairing for fine-tuning on the IoU)."""
+    return LovaszSegLoss(num_classes, ce=ce, tversky=0.0, class_weight=class_weight, ignore_index=ignore_index,
+                         lovasz=lovasz, classes=classes, per_image=per_image, schedule=schedule)

@@ -1818,6 +1818,144 @@ def seg_hard(logits: torch.Tensor, target: torch.Tensor, params, gamma: float = 
                             int(ignore_index), rows, bool(include_background), bool(with_stats))
 
 
+_SORT_DTYPES = (torch.int32, torch.uint32)
+
+
+def sort_pairs_tile() -> int:
+    """The pairs one workgroup of csu_sort_pairs ranks per pass."""
+    return int(lib().csu_sort_pairs_tile())
+
+
+def sort_pairs(keys: torch.Tensor, vals: torch.Tensor, segments: int, key_bits: int = 32):
+    """csu_sort_pairs: a stable sort of (key, value) pairs of 32-bit words (int32 or uint32 device tensors of one
+    size, read as unsigned bit patterns), independently in each of ``segments`` equal contiguous runs, ascending by
+    the low ``key_bits`` bits of the keys (csrc/sort_pairs.hip).  Returns new (keys, vals) tensors; the inputs are
+    left alone.  No synchronisation."""
+    require_device(keys, vals)
+    if keys.dtype not in _SORT_DTYPES or vals.dtype not in _SORT_DTYPES or keys.numel() < 1 or vals.shape != keys.shape:
+        raise ValueError("sort_pairs: non-empty int32 or uint32 keys and values of one shape")
+    segments, key_bits, n = int(segments), int(key_bits), keys.numel()
+    if segments < 1 or n % segments or n >= 1 << 31:
+        raise ValueError("sort_pairs: segments >= 1 equal runs, fewer than 2^31 pairs in all")
+    if not 1 <= key_bits <= 32:
+        raise ValueError("sort_pairs: 1 <= key_bits <= 32")
+    dev = keys.device
+    k, v = torch.empty(keys.shape, dtype=keys.dtype, device=dev), torch.empty(vals.shape, dtype=vals.dtype, device=dev)
+    k.copy_(keys)
+    v.copy_(vals)
+    ka, va = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    length = n // segments
+    nws = lib().csu_sort_pairs_workspace(segments, length)
+    ws = torch.empty(nws // 4, dtype=torch.int32, device=dev)
+    passes = (key_bits + 7) // 8
+    _launch("sort_pairs", lambda: lib().csu_sort_pairs(segments, length, key_bits, ptr(k), ptr(v), ptr(ka), ptr(va), ptr(ws),
+                                                       nws, stream_ptr(dev)),
+            0, 20 * n * passes, prec="f32")
+    return k, v
+
+
+class _SegLovaszFn(torch.autograd.Function):
+    """_SegCEFn's loss plus the Lovasz-Softmax term w_lv[0] * LS (csu_seg_lovasz_fwd / csu_seg_lovasz_bwd: the same
+    kernels with one more compile-time flag, csu_sort_pairs for the descending order of the per-pixel errors, an
+    integer scan and a coefficient pass).  class_mask: bit c = class c carries the term; w_lv: a one-element fp32
+    device tensor the kernels read, so its value may change between replays of a captured graph.  Also returns
+    terms = (loss without the term, LS) as a non-differentiable fp32 (2,) tensor; with debug the sorted keys and
+    values (uint32 bit patterns in int32 tensors) and the coefficient planes psi, all (|C|, B, HW)."""
+
+    @staticmethod
+    def forward(ctx, z, t, w_lv, params, cw, ignore_index: int, rows: int, include_background: bool, class_mask: int,
+                present_only: bool, per_image: bool, with_stats: bool = False, debug: bool = False):
+        B, K = z.shape[0], z.shape[1]
+        z, sb, sk, sp, HW, pad_ok = _seg_ce_layout(z)
+        t = t.contiguous()
+        w_ce, w_tv, alpha, beta, smooth = (float(v) for v in params)
+        dev = z.device
+        nc = bin(class_mask).count("1")
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(2, dtype=torch.float32, device=dev)
+        stats = torch.empty(3, K, dtype=torch.float64, device=dev) if with_stats else None
+        coef = torch.empty(2 * rows * K + 2, dtype=torch.float32, device=dev)
+        skeys = torch.empty(nc, B, HW, dtype=torch.int32, device=dev)
+        svals = torch.empty(nc, B, HW, dtype=torch.int32, device=dev)
+        psi = torch.empty(nc, B, HW, dtype=torch.float32, device=dev)
+        nws = lib().csu_seg_lovasz_workspace(B, K, HW, class_mask, int(per_image))
+        ws = torch.empty(nws // 8, dtype=torch.int64, device=dev)
+        lab = 1 if t.dtype == torch.int64 else 0
+        geom = (B, K, HW, rows, dtype_code(z), sb, sk, sp, int(pad_ok), lab, int(ignore_index), int(include_background),
+                int(class_mask))
+        nbytes = B * K * HW * z.element_size() + B * HW * t.element_size()
+        # the keys and values written, four sort passes of 20 B a pair, the count, the coefficient pass and psi
+        lv_bytes = nc * B * HW * (8 + 4 * 20 + 4 + 8 + 4)
+        _launch("seg_lovasz", lambda: lib().csu_seg_lovasz_fwd(B, K, HW, rows, geom[4], ptr(z), sb, sk, sp, geom[8], lab,
+                                                               ptr(t), geom[10], ptr(cw), w_ce, w_tv, alpha, beta, smooth,
+                                                               geom[11], geom[12], int(present_only), int(per_image),
+                                                               ptr(w_lv), ptr(skeys), ptr(svals), ptr(psi), ptr(loss),
+                                                               ptr(terms), ptr(stats), ptr(coef), ptr(ws), nws,
+                                                               stream_ptr(dev)),
+                (12 * K + 30) * B * HW, nbytes + lv_bytes, prec="f32")
+        ctx.save_for_backward(z, t, psi, w_lv, coef, cw)
+        ctx.seg = (geom, w_ce, w_tv, nbytes + 4 * nc * B * HW)
+        out = (loss, terms) + ((stats,) if with_stats else ()) + ((skeys, svals, psi) if debug else ())
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        z, t, psi, w_lv, coef, cw = ctx.saved_tensors
+        (B, K, HW, rows, dt, sb, sk, sp, pad_ok, lab, ignore, bg, mask), w_ce, w_tv, nbytes = ctx.seg
+        g = g.float().contiguous()
+        es = z.element_size()      # dz: the logits' strides and offset within 16 B, as _SegCEFn.backward
+        off = (z.data_ptr() % 16) // es
+        need = (B - 1) * sb + (HW - 1) * sp + max((K - 1) * sk + 1, _seg_ce_bucket(K) if pad_ok else 0)
+        dz = torch.empty(off + need, dtype=z.dtype, device=z.device).as_strided(z.shape, z.stride(), off)
+        _launch("seg_lovasz_bwd", lambda: lib().csu_seg_lovasz_bwd(B, K, HW, rows, dt, ptr(z), sb, sk, sp, pad_ok, lab, ptr(t),
+                                                                   ignore, ptr(cw), ptr(g), ptr(coef), w_ce, w_tv, bg, mask,
+                                                                   ptr(psi), ptr(w_lv), ptr(dz), stream_ptr(z.device)),
+                (18 * K + 20) * B * HW, nbytes + B * K * HW * es, prec="f32")
+        return (dz,) + (None,) * 12
+
+
+def seg_lovasz(logits: torch.Tensor, target: torch.Tensor, w_lv: torch.Tensor, params, classes=None,
+               present_only: bool = True, per_image: bool = False, class_weight: Optional[torch.Tensor] = None,
+               ignore_index: int = -100, rows: int = 1, include_background: bool = True, with_stats: bool = False,
+               debug: bool = False):
+    """seg_ce's loss plus w_lv[0] times the Lovasz-Softmax term (see _SegLovaszFn).  w_lv: a one-element fp32 device
+    tensor; params = (w_ce, w_tversky, alpha, beta, smooth), where both weights may be zero; classes: the classes
+    that carry the term (None: all); present_only: only the segments with a foreground pixel count; per_image: a
+    segment is one (image, class) pair instead of one class over the batch.  Returns (loss, terms[, stats][,
+    sorted_keys, sorted_vals, psi]); terms = (loss without the term, LS)."""
+    require_device(logits, target, w_lv, class_weight)
+    if logits.dim() < 2 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("seg_lovasz: fp32 or bf16 logits (B, K, *spatial)")
+    B, K = logits.shape[0], logits.shape[1]
+    if not 2 <= K <= SEG_CE_MAX_CLASSES:
+        raise ValueError(f"seg_lovasz: 2 <= K <= {SEG_CE_MAX_CLASSES} classes (got {K})")
+    if target.dtype not in (torch.int64, torch.uint8) or tuple(target.shape) != (B,) + tuple(logits.shape[2:]):
+        raise ValueError("seg_lovasz: int64 or uint8 target of the logits' shape without the class dim")
+    if logits.numel() < 1:
+        raise ValueError("seg_lovasz: empty logits")
+    if w_lv.dtype != torch.float32 or w_lv.numel() != 1:
+        raise ValueError("seg_lovasz: w_lv is a one-element fp32 tensor")
+    cls = sorted(set(range(K) if classes is None else (int(c) for c in classes)))
+    if not cls or cls[0] < 0 or cls[-1] >= K:
+        raise ValueError(f"seg_lovasz: classes is a non-empty set of classes in [0, {K})")
+    if len(cls) * (logits.numel() // K) >= 1 << 31:
+        raise ValueError("seg_lovasz: classes x pixels of the batch must stay below 2^31")
+    rows = int(rows)
+    if rows not in (1, B):
+        raise ValueError("seg_lovasz: rows must be 1 or the batch size")
+    if len(params) != 5:
+        raise ValueError("seg_lovasz: params = (w_ce, w_tversky, alpha, beta, smooth)")
+    if class_weight is not None:
+        if class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (K,):
+            raise ValueError("seg_lovasz: class_weight is an fp32 (K,) tensor")
+        class_weight = class_weight.contiguous()
+    mask = sum(1 << c for c in cls)
+    return _SegLovaszFn.apply(logits, target, w_lv.detach(), tuple(params), class_weight, int(ignore_index), rows,
+                              bool(include_background), mask, bool(present_only), bool(per_image), bool(with_stats),
+                              bool(debug))
+
+
 SIGNED_DISTANCE_MAX_DIM = 16383
 
 

@@ -1088,6 +1088,69 @@ int csu_seg_hard_bwd(int B, int K, long HW, int rows, int dtype, const void* z, 
                      const float* keys, void* dz, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Stable segmented radix sort of (uint32 key, uint32 value) pairs (csrc/sort_pairs.hip): the order of the
+ * Lovasz-Softmax loss below; the reference has no counterpart.
+ *   keys, vals: segments x len pairs on the device, `segments` contiguous runs of `len` pairs.  Each run is
+ *               sorted on its own, ascending by the low key_bits (1 .. 32) bits of the key; the bits above
+ *               are carried along and ignored.  Pairs with equal keys keep their order (stable).  The
+ *               result lands in keys / vals; keys_alt / vals_alt (the same size) are scratch.
+ * An LSD sort by 8-bit digits, ceil(key_bits / 8) passes of three launches: a digit histogram per tile of
+ * csu_sort_pairs_tile() pairs, a scan of every digit's row of tile counts, and a scatter that ranks a
+ * tile's pairs with wave ballots in their order.  Integers only, no atomics on global memory, nothing to
+ * clear: bitwise repeatable and a function of the input alone.  Nothing returns to the host, and no loop
+ * bound is read from device memory.  Workspace csu_sort_pairs_workspace(segments, len) bytes, 4-byte
+ * aligned (0: bad arguments).
+ * CSU_E_ARG: segments < 1, len < 1, segments * len >= 2^31, key_bits outside 1 .. 32, a null or misaligned
+ * pointer.  CSU_E_WORKSPACE: a null or short workspace.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_sort_pairs_workspace(int segments, long len);
+int csu_sort_pairs(int segments, long len, int key_bits, uint32_t* keys, uint32_t* vals, uint32_t* keys_alt,
+                   uint32_t* vals_alt, void* workspace, size_t ws_bytes, void* stream);
+int csu_sort_pairs_tile(void);
+
+/* ---------------------------------------------------------------------------------------
+ * The multi-class loss with the Lovasz-Softmax term (Berman, Triki, Blaschko, CVPR 2018), the convex
+ * surrogate of the mean IoU; csrc/seg_ce.hip, the kernels above with one more compile-time flag, and
+ * csu_sort_pairs.  The reference has no counterpart.  Every argument of csu_seg_ce_* keeps its meaning; added:
+ *   class_mask:   bit c set = class c carries the term (the set C, |C| >= 1, no bit at or above K).
+ *   present_only: 1 = only the segments with a foreground pixel count (Berman's "present"), 0 = all of C.
+ *   per_image:    0 = a segment is one class over the whole batch, 1 = one (image, class) pair.
+ *   w_lv:         one float on the device, read by the kernels, so a schedule can change the weight between
+ *                 replays of a captured graph.  It is not checked.
+ *   sorted_keys, sorted_vals: uint32 (|C|, B, HW), written by fwd: per segment in sorted order
+ *                 key = (dead ? 1 << 30 : 0) | (0x3F800000 - bits(e)), value = (fg << 31) | flat index in the
+ *                 segment (b HW + pix, or pix with per_image).  A dead pixel (label = ignore_index) has e = 0.
+ *   psi:          fp32 (|C|, B, HW), fully written by fwd and read by bwd: dLS / dp_c of every pixel.
+ * For a segment of class c with n live pixels in ascending flat index, p = softmax(z):
+ *   fg_i = [t_i = c],  e_i = fminf(fg_i ? sum_{k != c} p_k : p_c, 1),  pi = descending e, ties in ascending index
+ *   G = sum fg;  for j = 1 .. n:  F = #fg among pi(1 .. j-1),  I = G - F,  U = I + (j - 1),
+ *   g_j = 1 / U (pi(j) foreground),  I / (U (U + 1)) (background),  1 (U = 0);   LS_seg = sum_j e_pi(j) g_j
+ *   LS = sum over the counted segments of LS_seg / (max(1, number counted) x (B if per_image else 1)), counted
+ *        within an image with per_image;   psi = -/+ g_rank scale (foreground / background), 0 for a dead pixel
+ *   loss[0] = [w_ce CE + w_tversky ...] + w_lv[0] LS;  terms[0] = the bracket, terms[1] = LS
+ *   dz_k   += dloss[0] w_lv[0] p_k (f_k - sum_c f_c p_c),   f_c = psi_c for c in C, else 0
+ * fwd: the csu_seg_ce forward with the keys and values written in the same pass, csu_sort_pairs on 31 key
+ * bits, a three-launch integer scan of the fg bits over the sorted order, a pass that forms g and psi in fp64
+ * from the integers and sums e g per tile in fp64, and a fixed-order finish.  coef: 2 rows K + 2 floats.
+ * Workspace csu_seg_lovasz_workspace(B, K, HW, class_mask, per_image) bytes (a multiple of 8), 8-byte aligned
+ * (0: bad arguments).  w_ce = w_tversky = 0 is legal here.  Deterministic: fixed-order sums only.  With
+ * w_lv[0] = 0 the loss and dz equal those of csu_seg_ce_* on the same inputs bit for bit.
+ * CSU_E_ARG: as csu_seg_ce_* (but for the two zero weights), an empty class_mask or one with a bit at or above
+ * K, |C| B HW >= 2^31, a null w_lv, sorted_keys, sorted_vals, psi or terms.
+ * ------------------------------------------------------------------------------------- */
+size_t csu_seg_lovasz_workspace(int B, int K, long HW, uint32_t class_mask, int per_image);
+int csu_seg_lovasz_fwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                       int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                       float w_ce, float w_tversky, float alpha, float beta, float smooth, int include_background,
+                       uint32_t class_mask, int present_only, int per_image, const float* w_lv, uint32_t* sorted_keys,
+                       uint32_t* sorted_vals, float* psi, float* loss, float* terms, double* stats, float* coef,
+                       void* workspace, size_t ws_bytes, void* stream);
+int csu_seg_lovasz_bwd(int B, int K, long HW, int rows, int dtype, const void* z, long s_b, long s_k, long s_pix,
+                       int pad_ok, int label_dtype, const void* t, long ignore_index, const float* class_weight,
+                       const float* dloss, const float* coef, float w_ce, float w_tversky, int include_background,
+                       uint32_t class_mask, const float* psi, const float* w_lv, void* dz, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mask-aligned batch augmentation (AugmentationTransform cswin:20-87 + the dataset's /255 and
  * HWC -> CHW, cswin:166-173), square S x S images: img uint8 (B, S, S, 3), mask uint8 (B, S, S),
  * params int32 (B, 7) on the device = {hflip, vflip, clockwise quarter turns 0..3, crop top,
